@@ -20,7 +20,13 @@ highest offered rate sustaining p99 <= 2 ms with zero timeouts and
 steps run at that rate on a persistent generator, so a "step" is a
 fixed batch of Q = 1M*N queries of pure query work (weak scaling).
 Queries are a uniform A+SRV mix over the tree; replies are verified
-NOERROR (noerror_frac reported). Note: this workload has no tensor compute — the reference is a
+NOERROR (noerror_frac reported).
+
+A plain run does only what the headline needs and calibrates with
+1-second probes; --full is the long-form run (2-second probes).
+--dump-outputs DIR writes the replies of the chain for the step's
+query set, and the last timed step's counters, as DIR/*.npy (see
+dump_outputs). Note: this workload has no tensor compute — the reference is a
 Node.js DNS server (BASELINE.json "north_star" records the tier
 mismatch); torch is used only for the multi-rank barrier contract.
 """
@@ -200,17 +206,21 @@ class BlastDaemon:
             self.proc.kill()
 
 
-def calibrate_rate(blast, capacity, slo_us):
+def calibrate_rate(blast, capacity, slo_us, probe_s=2.0):
     """qps@SLO discovery (untimed): binary-search the highest offered
     rate that sustains p99 <= SLO with zero timeouts and >=97%
     delivery. Near the edge single probes are flaky (rare ~10 ms
-    stall events land in p99 or miss it), so a rate must pass TWO
-    consecutive 2-second probes, and the chosen point keeps a 3%
-    margin + one final confirmation. Fixed-rate steps at that point
-    are comparable round over round, unlike the chaotic closed-loop
-    saturation equilibrium (profiles/SCALING.md)."""
+    stall events land in p99 or miss it), so every level, and the
+    final confirmation, is decided by 2 of up to 3 probes of probe_s
+    seconds each, and the chosen point keeps a 3% margin. Fixed-rate
+    steps at that point are comparable round over round, unlike the
+    chaotic closed-loop saturation equilibrium (profiles/SCALING.md).
+
+    The search takes up to 18 probes, so probe_s sets what calibration
+    costs a run: a plain run uses 1-second probes to keep its setup
+    short, --full the longer 2-second ones."""
     def probe(rate, tag):
-        q = max(400_000, int(rate * 2.0))
+        q = max(int(200_000 * probe_s), int(rate * probe_s))
         r = blast.step(q, rate=rate)
         good = (r["timeouts"] == 0 and r["p99_us"] <= slo_us and
                 r["qps"] >= 0.97 * rate)
@@ -219,25 +229,88 @@ def calibrate_rate(blast, capacity, slo_us):
             f"{'OK' if good else 'FAIL'}")
         return good
 
+    def vote(rate, tag):
+        # one transient flake, in either direction, must not decide a
+        # level (a single stray FAIL near the top used to halve the
+        # whole bracket): two probes, and a third when they disagree
+        a = probe(rate, f"{tag}a")
+        b = probe(rate, f"{tag}b")
+        return a if a == b else probe(rate, f"{tag}c")
+
     lo, hi = 0.45 * capacity, 1.02 * capacity
     best = 0.0
     for i in range(5):
         mid = (lo + hi) / 2
-        a = probe(mid, f"bisect{i}a")
-        b = probe(mid, f"bisect{i}b") if a else False
-        if a and not b:
-            # one transient flake must not collapse the search:
-            # 2-of-3 consecutive probes decide the level
-            b = probe(mid, f"bisect{i}c")
-        if a and b:
+        if vote(mid, f"bisect{i}"):
             best = mid
             lo = mid
         else:
             hi = mid
     rate = 0.97 * (best if best > 0 else lo)
-    if not probe(rate, "confirm"):
+    if not vote(rate, "confirm"):
         rate *= 0.93
     return rate
+
+
+DUMP_MAX_NAMES = 8192
+
+
+def dump_outputs(out_dir, last, names_file, port):
+    """--dump-outputs: what the serving chain computed, as .npy files
+    that two builds can be compared by.
+
+    last_step_counters.npy  float64[5]: sent, received, timeouts,
+        noerror, other_rcode of the last timed step (the part of the
+        step's result that does not depend on timing).
+    replies.npy  float64[names, 4]: one row per query name of the
+        step's query set, in names-file order (a fixed seeded sample
+        of DUMP_MAX_NAMES rows for larger trees): rcode, answer count,
+        additional count, and a checksum of the answer + additional
+        records that ignores their order (member order is shuffled
+        per reply by design). dnsblast keeps only counters of the
+        replies it receives, so after the last step every name is
+        asked once more, untimed, through the same balancer ->
+        binderd chain.
+    """
+    import random
+    import zlib
+
+    import numpy as np
+
+    from binder_amd.digclient import dig
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "last_step_counters.npy", np.array(
+        [last[k] for k in ("sent", "received", "timeouts", "noerror",
+                           "other_rcode")], dtype=np.float64))
+
+    names = [ln.split() for ln in
+             Path(names_file).read_text().splitlines() if ln]
+    if len(names) > DUMP_MAX_NAMES:
+        keep = sorted(random.Random(0).sample(range(len(names)),
+                                              DUMP_MAX_NAMES))
+        names = [names[i] for i in keep]
+    rcodes = ["NOERROR", "FORMERR", "SERVFAIL", "NXDOMAIN", "NOTIMP",
+              "REFUSED"]
+    rows = np.zeros((len(names), 4), dtype=np.float64)
+    for i, (name, qtype) in enumerate(names):
+        for attempt in range(3):  # UDP: a lost datagram is re-asked
+            try:
+                r = dig(name, qtype, server="127.0.0.1", port=port,
+                        timeout=2.0)
+                break
+            except OSError:
+                if attempt == 2:
+                    raise
+        recs = r["answers"] + r["additionals"]
+        rows[i] = (rcodes.index(r["rcode"]) if r["rcode"] in rcodes
+                   else -1,
+                   len(r["answers"]), len(r["additionals"]),
+                   sum(zlib.crc32(json.dumps(rec, sort_keys=True)
+                                  .encode()) for rec in recs))
+    np.save(out_dir / "replies.npy", rows)
+    log(f"dumped {len(names)} replies + last-step counters to {out_dir}")
 
 
 def main():
@@ -252,6 +325,13 @@ def main():
     ap.add_argument("--churn-qps", type=int, default=0,
                     help="ZK mutations/sec during timed steps "
                          "(BASELINE config 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the chain's "
+                         "replies and the last step's counters to "
+                         "DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="long-form run: calibrate the operating "
+                         "point with 2-second probes (plain: 1 s)")
     args = ap.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -361,7 +441,8 @@ def main():
             elif not closed_loop:
                 # qps@SLO protocol: fixed offered rate for the timed
                 # steps, discovered against the SLO (untimed)
-                rate = calibrate_rate(blast, capacity, slo_us)
+                rate = calibrate_rate(blast, capacity, slo_us,
+                                      probe_s=2.0 if args.full else 1.0)
                 log(f"operating point: {rate:.0f} qps offered "
                     f"(capacity {capacity:.0f}, SLO p99<={slo_us}us)")
             for _ in range(args.warmup):
@@ -414,6 +495,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
 
+        if rank == 0 and args.dump_outputs and last is not None:
+            dump_outputs(args.dump_outputs, last, names_file, bal_port)
+
         if rank == 0:
             total_queries = args.steps * q_step
             qps = total_queries / elapsed
@@ -439,6 +523,7 @@ def main():
                     "protocol": ("closed-loop" if closed_loop else
                                  f"fixed-rate@SLO(p99<={slo_us}us)"),
                     "offered_qps": int(rate) if rank == 0 else None,
+                    "calibration_probe_s": 2.0 if args.full else 1.0,
                     "tree_records": args.tree_records,
                     "churn_qps": args.churn_qps,
                     "query_mix": "A+SRV uniform",

@@ -195,7 +195,7 @@ def config4(tmp, n_queries):
 
 def config5(tmp, n_queries):
     out = subprocess.run(
-        [sys.executable, str(REPO / "bench.py"), "--gpus", "4",
+        [sys.executable, str(REPO / "bench.py"), "--full", "--gpus", "4",
          "--tree-records", "100000", "--churn-qps", "1000",
          "--steps", "2", "--warmup", "1",
          "--queries-per-proc", str(n_queries // 4)],

@@ -29,10 +29,14 @@ def last_json_line(text):
 
 
 @pytest.mark.timeout(300)
-def test_bench_single_process_schema():
+def test_bench_single_process_schema(tmp_path):
+    import numpy as np
+
+    dump = tmp_path / "dump"
     out = subprocess.run(
         [sys.executable, str(REPO_ROOT / "bench.py"), "--steps", "1",
-         "--warmup", "0", "--queries-per-proc", "20000"],
+         "--warmup", "0", "--queries-per-proc", "20000",
+         "--dump-outputs", str(dump)],
         capture_output=True, text=True, timeout=280, cwd=REPO_ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = last_json_line(out.stdout)
@@ -44,6 +48,24 @@ def test_bench_single_process_schema():
     assert d["scaling"] == "weak"
     assert d["data"] == "synthetic"
     assert d["config"]["tree_records"] == 10000
+    assert d["steps"] == 1 and d["ms_per_step"] > 0
+    assert d["config"]["calibration_probe_s"] == 1.0
+
+    # --dump-outputs: the last step's counters and one reply row per
+    # query name (5000 hosts + 1000 services x (A, SRV))
+    counters = np.load(dump / "last_step_counters.npy")
+    assert counters.dtype == np.float64
+    sent, received, timeouts, noerror, other = counters
+    # dnsblast splits the step evenly over its threads (<= 16)
+    assert 20000 - 16 < sent <= 20000
+    assert sent == received == noerror
+    assert timeouts == other == 0
+    replies = np.load(dump / "replies.npy")
+    assert replies.dtype == np.float64 and replies.shape == (7000, 4)
+    assert (replies[:, 0] == 0).all()           # NOERROR
+    assert (replies[:5000, 1] == 1).all()       # host: one A
+    assert (replies[5000:, 1] == 4).all()       # service: 4 members
+    assert (replies[:, 3] > 0).all()
 
 
 @pytest.mark.timeout(600)
@@ -78,8 +100,10 @@ def test_calibration_converges_and_tolerates_flakes():
     class FakeBlast:
         def __init__(self, flake_prob=0.0):
             self.flake_prob = flake_prob
+            self.seconds = []
 
         def step(self, queries, rate=0):
+            self.seconds.append(queries / rate)
             ok = rate <= true_limit
             if ok and rng.random() < self.flake_prob:
                 ok = False  # transient stall lands in p99
@@ -97,3 +121,13 @@ def test_calibration_converges_and_tolerates_flakes():
     r = bench.calibrate_rate(FakeBlast(flake_prob=0.2),
                              capacity=4_000_000, slo_us=2000)
     assert 0.70 * true_limit <= r <= true_limit, r
+
+    # probe_s sets how long each probe offers load (--full: 2 s,
+    # plain: 1 s); the search itself is unchanged
+    for probe_s in (2.0, 1.0):
+        fb = FakeBlast()
+        r = bench.calibrate_rate(fb, capacity=4_000_000, slo_us=2000,
+                                 probe_s=probe_s)
+        assert 0.85 * true_limit <= r <= true_limit, r
+        assert len(fb.seconds) <= 18
+        assert all(abs(s - probe_s) < 1e-3 for s in fb.seconds)
