@@ -32,7 +32,7 @@ PY_EXT_SUFFIX := $(shell $(PYTHON)-config --extension-suffix 2>/dev/null || echo
 PY_INCLUDES := $(shell $(PYTHON) -m pybind11 --includes)
 PYMOD := binder_amd/_native$(PY_EXT_SUFFIX)
 
-BINARIES := bin/binderd bin/binder-balancer bin/dnsblast \
+BINARIES := bin/binderd bin/binder-balancer bin/dnsblast bin/bsockblast \
 	bin/binder-adjust bin/binder-supervisor bin/zklogcat bin/zktool \
 	bin/zkd
 
@@ -49,6 +49,10 @@ bin/binder-balancer: $(CORE_OBJS) $(BUILD)/native/balancer/balancer_main.o
 bin/dnsblast: $(CORE_OBJS) $(BUILD)/native/bench/dnsblast_main.o
 	@mkdir -p bin
 	$(CXX) $(CXXFLAGS) $^ -o $@ $(LDFLAGS) -lpthread
+
+bin/bsockblast: $(CORE_OBJS) $(BUILD)/native/bench/bsockblast_main.o
+	@mkdir -p bin
+	$(CXX) $(CXXFLAGS) $^ -o $@ $(LDFLAGS)
 
 bin/binder-adjust: $(CORE_OBJS) $(BUILD)/native/adjust/adjust_main.o
 	@mkdir -p bin
@@ -96,6 +100,19 @@ check: all
 	$(PYTHON) tools/lint.py
 	@echo "check OK"
 
+# Sanitizer run of the balancer-socket receive buffer (framebuf.hpp) in
+# a stand-alone program: random frame streams, random split points, one
+# maximum-size frame. Host-only, CPU-only.
+$(BUILD)/framebuf_check: native/server/framebuf_check_main.cpp \
+		native/server/framebuf.hpp native/balancer/protocol.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-framebuf: $(BUILD)/framebuf_check
+	$(BUILD)/framebuf_check 1 40
+
 # release tarball layout under /opt/binder-amd (the reference ships
 # /opt/smartdc/binder with balancer+smf_adjust in lib/ and zklog in
 # bin/; Makefile:178-229 there)
@@ -121,4 +138,4 @@ clean:
 
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
-.PHONY: all clean test check release
+.PHONY: all clean test check check-framebuf release

@@ -98,6 +98,10 @@ struct CompiledRecord {
         };
         std::vector<Member> members;
         uint16_t srvAnCount = 0;  /* total SRV records over members */
+        /* byte size of the whole A / SRV response (head + every
+         * member's segments); member order does not change it */
+        size_t totalA = 0;
+        size_t totalSrv = 0;
     };
     mutable std::unique_ptr<ServiceCache> svc;
     void clearWireCaches() const {

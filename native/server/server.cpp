@@ -19,13 +19,46 @@ void fillClientInfo(ClientInfo& ci, const struct sockaddr_storage& ss,
     ci.family = family;
     if (ss.ss_family == AF_INET) {
         const auto* sa = (const struct sockaddr_in*)&ss;
-        inet_ntop(AF_INET, &sa->sin_addr, ci.address, sizeof(ci.address));
+        memcpy(ci.addr, &sa->sin_addr, 4);
+        ci.ipFamily = 4;
         ci.port = ntohs(sa->sin_port);
     } else if (ss.ss_family == AF_INET6) {
         const auto* sa = (const struct sockaddr_in6*)&ss;
-        inet_ntop(AF_INET6, &sa->sin6_addr, ci.address, sizeof(ci.address));
+        memcpy(ci.addr, &sa->sin6_addr, 16);
+        ci.ipFamily = 6;
         ci.port = ntohs(sa->sin6_port);
     }
+}
+
+const char* ClientInfo::address(char (&buf)[48]) const {
+    buf[0] = '\0';
+    if (ipFamily == 4)
+        inet_ntop(AF_INET, addr, buf, sizeof(buf));
+    else if (ipFamily == 6)
+        inet_ntop(AF_INET6, addr, buf, sizeof(buf));
+    return buf;
+}
+
+void ReplySink::open(size_t dnsLen) {
+    if (vec_ != nullptr) {
+        vec_->clear();
+        vec_->reserve(dnsLen);
+        return;
+    }
+    uint32_t plen = (uint32_t)(4 + dnsLen);
+    uint8_t head[bsock::kHeaderLen + 4];
+    head[0] = bsock::kMagic;
+    head[1] = bsock::FRAME_REPLY;
+    head[2] = (uint8_t)plen;
+    head[3] = (uint8_t)(plen >> 8);
+    head[4] = (uint8_t)(plen >> 16);
+    head[5] = (uint8_t)(plen >> 24);
+    head[6] = (uint8_t)reqId_;
+    head[7] = (uint8_t)(reqId_ >> 8);
+    head[8] = (uint8_t)(reqId_ >> 16);
+    head[9] = (uint8_t)(reqId_ >> 24);
+    frames_->append((const char*)head, sizeof(head));
+    start_ = frames_->size();
 }
 
 DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
@@ -41,6 +74,10 @@ DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
         "total time to process Binder requests");
     sizeHist_ = collector->histogram("binder_response_size_bytes",
                                      "size in bytes of Binder responses");
+
+    const EngineConfig& cfg = engine_->config();
+    if (!cfg.dnsDomain.empty()) dotDomain_ = "." + cfg.dnsDomain;
+    dcSuffix_ = cfg.dnsDomain + "." + cfg.datacenterName;
 
     rxArena_.resize(kBatch * kInBuf);
     rxHdrs_.resize(kBatch);
@@ -355,12 +392,17 @@ static void buildServiceCache(const StoreNode* node,
     buildHead(cache->headA, key, 1, (uint16_t)cache->members.size(), 0);
     buildHead(cache->headSrv, srvQname, 33, cache->srvAnCount,
               (uint16_t)cache->members.size());
+    cache->totalA = cache->headA.size();
+    cache->totalSrv = cache->headSrv.size();
+    for (const auto& m : cache->members) {
+        cache->totalA += m.aSeg.size();
+        cache->totalSrv += m.srvSeg.size() + m.addSeg.size();
+    }
     rec.svc = std::move(cache);
 }
 
 bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
-                         const ClientInfo& ci,
-                         std::vector<uint8_t>& out) {
+                         const ClientInfo& ci, ReplySink& out) {
     /* debug/trace want the slow path's extra detail; info-level
      * per-query lines are emitted here from cached fragments */
     if (log_.enabled(LogLevel::Debug)) return false;
@@ -437,8 +479,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
                    s.substr(s.size() - suf.size()) == suf;
         };
         if (endsWith(stripped, cfg.dnsDomain)) return false;
-        std::string dcsuff = cfg.dnsDomain + "." + cfg.datacenterName;
-        if (endsWith(stripped, dcsuff)) return false;
+        if (endsWith(stripped, dcSuffix_)) return false;
     }
 
     const Store* store = engineStore_;
@@ -452,11 +493,11 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
     auto logOpen = [&](const char* qtype) -> std::string& {
         std::string& f = logFields_;
         f.clear();
-        char nb[96];
+        char nb[96], ab[48];
         uint16_t qid = (uint16_t)(((uint16_t)data[0] << 8) | data[1]);
         snprintf(nb, sizeof(nb),
                  ",\"req_id\":%u,\"client\":\"%s\",\"port\":\"%u/%s\"",
-                 (unsigned)qid, ci.address, (unsigned)ci.port,
+                 (unsigned)qid, ci.address(ab), (unsigned)ci.port,
                  ci.family);
         f += nb;
         f += ",\"query\":{\"name\":\"";
@@ -474,19 +515,13 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         if (isSrv &&
             (srvSvc_ != rec.srvce || srvProto_ != rec.proto))
             return false;  /* slow path: NXDOMAIN */
-        if (!rec.svc) {
-            const std::string& dd = cfg.dnsDomain;
-            buildServiceCache(node, key, dd.empty() ? dd : "." + dd);
-        }
+        if (!rec.svc) buildServiceCache(node, key, dotDomain_);
         const CompiledRecord::ServiceCache& c = *rec.svc;
         if (!c.usable) return false;
 
         /* size check against the UDP limit; oversize => slow path
          * (which truncates with TC exactly as before) */
-        size_t total = (isSrv ? c.headSrv.size() : c.headA.size());
-        for (const auto& m : c.members)
-            total += isSrv ? m.srvSeg.size() + m.addSeg.size()
-                           : m.aSeg.size();
+        size_t total = isSrv ? c.totalSrv : c.totalA;
         if (udp && total > 512) return false;
 
         /* Fisher-Yates member order (server.js:40-53, 361) */
@@ -499,28 +534,28 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
             std::swap(shuffleIdx_[i], shuffleIdx_[j]);
         }
 
-        out.clear();
-        out.reserve(total);
+        out.open(total);
         const auto& head = isSrv ? c.headSrv : c.headA;
-        out.insert(out.end(), head.begin(), head.end());
+        out.append(head.data(), head.size());
         if (isSrv) {
             for (size_t i = 0; i < n; ++i) {
                 const auto& m = c.members[shuffleIdx_[i]];
-                out.insert(out.end(), m.srvSeg.begin(), m.srvSeg.end());
+                out.append(m.srvSeg.data(), m.srvSeg.size());
             }
             for (size_t i = 0; i < n; ++i) {
                 const auto& m = c.members[shuffleIdx_[i]];
-                out.insert(out.end(), m.addSeg.begin(), m.addSeg.end());
+                out.append(m.addSeg.data(), m.addSeg.size());
             }
         } else {
             for (size_t i = 0; i < n; ++i) {
                 const auto& m = c.members[shuffleIdx_[i]];
-                out.insert(out.end(), m.aSeg.begin(), m.aSeg.end());
+                out.append(m.aSeg.data(), m.aSeg.size());
             }
         }
-        out[0] = data[0];
-        out[1] = data[1];
-        out[2] = (uint8_t)(out[2] | (data[2] & 0x01));
+        uint8_t* w = out.dns();
+        w[0] = data[0];
+        w[1] = data[1];
+        w[2] = (uint8_t)(w[2] | (data[2] & 0x01));
 
         ++served_;
         static const std::string kLabelSrv = "type=\"SRV\"";
@@ -531,7 +566,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         ++*(isSrv ? fpCntSrv_ : fpCntA_);
         latHist_->observeFast(*(isSrv ? fpLatSrv_ : fpLatA_), 1e-6);
         sizeHist_->observeFast(*(isSrv ? fpSizeSrv_ : fpSizeA_),
-                               (double)out.size());
+                               (double)total);
         if (log_.enabled(LogLevel::Info)) {
             std::string& f = logOpen(isSrv ? "SRV" : "A");
             bool lfirst = true;
@@ -557,7 +592,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
             f += kLogClose;
             log_.logRaw(LogLevel::Info, "DNS query", f);
         }
-        BAMD_PROBE2("op-req-done", out.size(), 0);
+        BAMD_PROBE2("op-req-done", total, 0);
         return true;
     }
 
@@ -581,16 +616,19 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         rec.logA.clear();
         jsonEscape("A " + m.answers[0].addrString(), rec.logA);
     }
-    out = rec.wireA;
-    out[0] = data[0];  /* id */
-    out[1] = data[1];
-    out[2] = (uint8_t)(out[2] | (data[2] & 0x01));  /* echo RD */
+    const size_t wlen = rec.wireA.size();
+    out.open(wlen);
+    out.append(rec.wireA.data(), wlen);
+    uint8_t* w = out.dns();
+    w[0] = data[0];  /* id */
+    w[1] = data[1];
+    w[2] = (uint8_t)(w[2] | (data[2] & 0x01));  /* echo RD */
 
     ++served_;
     if (fpCntA_ == nullptr) initFastMetricSlots();
     ++*fpCntA_;
     latHist_->observeFast(*fpLatA_, 1e-6);  /* sub-us */
-    sizeHist_->observeFast(*fpSizeA_, (double)out.size());
+    sizeHist_->observeFast(*fpSizeA_, (double)wlen);
     if (log_.enabled(LogLevel::Info)) {
         std::string& f = logOpen("A");
         f += rec.logA;
@@ -598,7 +636,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         f += kLogClose;
         log_.logRaw(LogLevel::Info, "DNS query", f);
     }
-    BAMD_PROBE2("op-req-done", out.size(), 0);
+    BAMD_PROBE2("op-req-done", wlen, 0);
     return true;
 }
 
@@ -634,10 +672,43 @@ static void appendReplyFrame(std::string& out, uint32_t reqId,
     out.append((const char*)dns, dnsLen);
 }
 
+std::function<void(std::vector<uint8_t>)> DnsServer::makeAsyncReply(
+    const ReplyTarget& t) {
+    switch (t.kind) {
+    case ReplyTarget::Kind::Udp: {
+        struct sockaddr_storage srcCopy = *t.src;
+        socklen_t srcLen = t.srcLen;
+        return [this, srcCopy, srcLen](std::vector<uint8_t> wire) {
+            sendto(udpFd_, wire.data(), wire.size(), 0,
+                   (const struct sockaddr*)&srcCopy, srcLen);
+        };
+    }
+    case ReplyTarget::Kind::Tcp: {
+        /* shared_ptr: the reply may outlive the connection */
+        std::shared_ptr<TcpConn> self = t.tcp->shared_from_this();
+        return [this, self](std::vector<uint8_t> wire) {
+            if (self->closed) return;
+            self->out.push_back((char)(wire.size() >> 8));
+            self->out.push_back((char)wire.size());
+            self->out.append((const char*)wire.data(), wire.size());
+            tcpFlush(self.get());
+        };
+    }
+    case ReplyTarget::Kind::Bal:
+        break;
+    }
+    std::shared_ptr<BalConn> self = t.bal->shared_from_this();
+    uint32_t reqId = t.reqId;
+    return [this, self, reqId](std::vector<uint8_t> wire) {
+        if (self->closed) return;
+        appendReplyFrame(self->out, reqId, wire.data(), wire.size());
+        balFlush(self.get());
+    };
+}
+
 bool DnsServer::process(const uint8_t* data, size_t len, bool udp,
-                        const ClientInfo& ci, std::vector<uint8_t>& out,
-                        std::function<void(std::vector<uint8_t>)>
-                            asyncReply) {
+                        const ClientInfo& ci, ReplySink& out,
+                        const ReplyTarget& target) {
     BAMD_PROBE2("op-req-start", len, (int)udp);
     if (fastPath(data, len, udp, ci, out)) return true;
     int64_t start = nowUs();
@@ -671,10 +742,11 @@ bool DnsServer::process(const uint8_t* data, size_t len, bool udp,
         ClientInfo ciCopy = ci;
         size_t lim = limit;
         bool edns = hasEdns;
+        auto asyncReply = makeAsyncReply(target);
         recursion_->resolve(
             *queryHeap, *respHeap,
             [this, respHeap, queryHeap, ciCopy, lim, edns, start,
-             asyncReply, qr]() {
+             asyncReply = std::move(asyncReply), qr]() {
                 if (edns)
                     respHeap->additionals.push_back(Record::OPT(1400));
                 auto wire = respHeap->encode(lim);
@@ -687,12 +759,23 @@ bool DnsServer::process(const uint8_t* data, size_t len, bool udp,
     }
 
     if (hasEdns) resp.additionals.push_back(Record::OPT(1400));
-    resp.encodeInto(out, limit);
+    size_t sent;
+    if (std::vector<uint8_t>* v = out.vec()) {
+        resp.encodeInto(*v, limit);
+        sent = v->size();
+    } else {
+        resp.encodeInto(encScratch_, limit);
+        sent = encScratch_.size();
+        if (sent != 0) {
+            out.open(sent);
+            out.append(encScratch_.data(), sent);
+        }
+    }
     QueryTimers tm;
     tm.parseUs = tParse - start;
     tm.resolveUs = tResolve - tParse;
     tm.encodeUs = nowUs() - tResolve;
-    afterQuery(query, resp, qr, ci, out.size(), start, tm);
+    afterQuery(query, resp, qr, ci, sent, start, tm);
     return true;
 }
 
@@ -724,14 +807,14 @@ void DnsServer::afterQuery(const Message& query, const Message& resp,
     if (!log_.enabled(lv)) return;
 
     const std::string& dd = engine_->config().dnsDomain;
-    std::string dotdd = dd.empty() ? "" : "." + dd;
+    const std::string& dotdd = dotDomain_;
     std::string& f = logFields_;
     std::string& s = logScratch_;
     f.clear();
-    char nbuf[96];
+    char nbuf[96], abuf[48];
     snprintf(nbuf, sizeof(nbuf),
              ",\"req_id\":%u,\"client\":\"%s\",\"port\":\"%u/%s\"",
-             (unsigned)query.header.id, ci.address, (unsigned)ci.port,
+             (unsigned)query.header.id, ci.address(abuf), (unsigned)ci.port,
              ci.family);
     f += nbuf;
     f += ",\"query\":{";
@@ -812,16 +895,14 @@ void DnsServer::onUdpReadable() {
             fillClientInfo(ci, rxAddrs_[i], "udp");
             std::vector<uint8_t>& out = txBufs_[nOut];
             out.clear();
-            struct sockaddr_storage srcCopy = rxAddrs_[i];
             socklen_t srcLen = rxHdrs_[i].msg_hdr.msg_namelen;
+            ReplySink sink(&out);
+            ReplyTarget target{ReplyTarget::Kind::Udp};
+            target.src = &rxAddrs_[i];  /* copied if it goes async */
+            target.srcLen = srcLen;
             bool sync = process(
                 rxArena_.data() + (size_t)i * kInBuf, rxHdrs_[i].msg_len,
-                true, ci, out,
-                [this, srcCopy, srcLen](std::vector<uint8_t> wire) {
-                    /* async (recursion) reply path */
-                    sendto(udpFd_, wire.data(), wire.size(), 0,
-                           (const struct sockaddr*)&srcCopy, srcLen);
-                });
+                true, ci, sink, target);
             if (sync && !out.empty()) {
                 txAddrs_[nOut] = rxAddrs_[i];
                 txIovs_[nOut].iov_base = out.data();
@@ -932,17 +1013,14 @@ void DnsServer::onTcpConn(TcpConn* c, uint32_t events) {
         size_t mlen = ((size_t)(uint8_t)c->in[0] << 8) |
                       (uint8_t)c->in[1];
         if (c->in.size() < 2 + mlen) break;
-        std::vector<uint8_t> out;
-        std::shared_ptr<TcpConn> self = keep;
+        std::vector<uint8_t>& out = tcpOut_;
+        out.clear();
+        ReplySink sink(&out);
+        ReplyTarget target{ReplyTarget::Kind::Tcp};
+        target.tcp = c;
         bool sync = process(
-            (const uint8_t*)c->in.data() + 2, mlen, false, c->ci, out,
-            [this, self](std::vector<uint8_t> wire) {
-                if (self->closed) return;
-                self->out.push_back((char)(wire.size() >> 8));
-                self->out.push_back((char)wire.size());
-                self->out.append((const char*)wire.data(), wire.size());
-                tcpFlush(self.get());
-            });
+            (const uint8_t*)c->in.data() + 2, mlen, false, c->ci, sink,
+            target);
         if (sync) {
             if (!out.empty()) {
                 c->out.push_back((char)(out.size() >> 8));
@@ -983,13 +1061,21 @@ void DnsServer::closeBal(BalConn* c) {
 }
 
 void DnsServer::balFlush(BalConn* c) {
-    while (!c->out.empty()) {
-        ssize_t nw = write(c->fd, c->out.data(), c->out.size());
+    while (c->outOff < c->out.size()) {
+        ssize_t nw = write(c->fd, c->out.data() + c->outOff,
+                           c->out.size() - c->outOff);
         if (nw > 0) {
-            c->out.erase(0, (size_t)nw);
+            c->outOff += (size_t)nw;
             continue;
         }
         if (nw < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
+            /* compact only past a large flushed prefix, so a peer that
+             * stays blocked does not keep it resident (amortized O(1)
+             * against the memmove-per-write of erase(0, nw)) */
+            if (c->outOff > (1u << 20)) {
+                c->out.erase(0, c->outOff);
+                c->outOff = 0;
+            }
             if (!c->writeBlocked) {
                 c->writeBlocked = true;
                 loop_->modFd(c->fd, EPOLLIN | EPOLLOUT);
@@ -999,6 +1085,8 @@ void DnsServer::balFlush(BalConn* c) {
         closeBal(c);
         return;
     }
+    c->out.clear();
+    c->outOff = 0;
     if (c->writeBlocked) {
         c->writeBlocked = false;
         loop_->modFd(c->fd, EPOLLIN);
@@ -1020,15 +1108,21 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
      * workers' connections wait - measured as bimodal multi-ms p99 at
      * N=1. Level-triggered epoll re-fires for the remainder, so
      * capping the read keeps per-event latency bounded and service
-     * across connections fair. */
+     * across connections fair.
+     *
+     * read() lands in the tail of the receive buffer (no bounce
+     * buffer). A short read means the socket is drained for now, so
+     * the EAGAIN round trip is skipped too; EOF shows on the next
+     * event. */
     constexpr size_t kMaxReadPerEvent = 128 * 1024;
     size_t got = 0;
-    char buf[16384];
     while (got < kMaxReadPerEvent) {
-        ssize_t nr = read(c->fd, buf, sizeof(buf));
+        size_t want = kMaxReadPerEvent - got;
+        ssize_t nr = read(c->fd, c->in.tail(want), want);
         if (nr > 0) {
-            c->in.append(buf, (size_t)nr);
+            c->in.commit((size_t)nr);
             got += (size_t)nr;
+            if ((size_t)nr < want) break;
             continue;
         }
         if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
@@ -1036,55 +1130,37 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
         return;
     }
 
-    while (c->in.size() >= bsock::kHeaderLen) {
-        const uint8_t* h = (const uint8_t*)c->in.data();
-        if (h[0] != bsock::kMagic) {
-            closeBal(c);
-            return;
-        }
-        uint8_t type = h[1];
-        uint32_t plen = bsock::getU32(h + 2);
-        if (plen > bsock::kMaxPayload) {
-            closeBal(c);
-            return;
-        }
-        if (c->in.size() < bsock::kHeaderLen + plen) break;
-        const uint8_t* payload = h + bsock::kHeaderLen;
-
-        if (type == bsock::FRAME_PING) {
+    /* Frames are parsed by advancing the buffer's cursor; the partial
+     * frame left at the end moves to the front once, below. */
+    bsock::FrameView fr;
+    bsock::FrameStatus st;
+    while ((st = bsock::nextFrame(c->in, fr)) == bsock::FrameStatus::Ok) {
+        if (fr.type == bsock::FRAME_PING) {
             bsock::appendFrame(c->out, bsock::FRAME_PONG, "");
-        } else if (type == bsock::FRAME_QUERY) {
+        } else if (fr.type == bsock::FRAME_QUERY) {
             bsock::QueryFrame qf;
-            if (bsock::parseQuery(payload, plen, qf)) {
+            if (bsock::parseQuery(fr.payload, fr.plen, qf)) {
                 ClientInfo ci;
                 ci.family = qf.proto == 1 ? "tcp" : "udp";
                 ci.port = qf.srcPort;
-                if (qf.family == 4)
-                    inet_ntop(AF_INET, qf.srcAddr, ci.address,
-                              sizeof(ci.address));
-                else
-                    inet_ntop(AF_INET6, qf.srcAddr, ci.address,
-                              sizeof(ci.address));
-                std::vector<uint8_t> out;
-                uint32_t reqId = qf.reqId;
-                bool udp = qf.proto == 0;
-                std::shared_ptr<BalConn> self = keep;
-                bool sync = process(
-                    qf.dns, qf.dnsLen, udp, ci, out,
-                    [this, self, reqId](std::vector<uint8_t> wire) {
-                        if (self->closed) return;
-                        appendReplyFrame(self->out, reqId,
-                                         wire.data(), wire.size());
-                        balFlush(self.get());
-                    });
-                if (sync && !out.empty()) {
-                    appendReplyFrame(c->out, qf.reqId, out.data(),
-                                     out.size());
-                }
+                ci.ipFamily = qf.family == 4 ? 4 : 6;
+                memcpy(ci.addr, qf.srcAddr, sizeof(ci.addr));
+                ReplySink sink(&c->out, qf.reqId);
+                ReplyTarget target{ReplyTarget::Kind::Bal};
+                target.bal = c;
+                target.reqId = qf.reqId;
+                process(qf.dns, qf.dnsLen, qf.proto == 0, ci, sink,
+                        target);
             }
         }
-        c->in.erase(0, bsock::kHeaderLen + plen);
     }
+    if (st == bsock::FrameStatus::Bad) {
+        closeBal(c);
+        return;
+    }
+    /* a synchronous recursion reply may have hit a write error */
+    if (c->closed) return;
+    c->in.compact();
     balFlush(c);
 }
 

@@ -28,6 +28,7 @@
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
 #include "../engine/engine.hpp"
+#include "framebuf.hpp"
 #include "metrics.hpp"
 
 namespace bamd {
@@ -45,10 +46,58 @@ struct QueryTimers {
     int64_t encodeUs = 0;
 };
 
+/* Who asked. The address stays in raw form: only the per-query log line
+ * wants the presentation string, and formatting it for every query was
+ * ~100 ns of inet_ntop that nothing read at warn level. */
 struct ClientInfo {
-    char address[48] = "";  // presentation form
+    uint8_t addr[16] = {};   // network order; first 4 bytes when ipFamily=4
+    uint8_t ipFamily = 0;    // 4, 6, or 0 = unknown (formats as "")
     uint16_t port = 0;
     const char* family = "udp";  // matches query.src.family usage in logs
+
+    /* presentation form, written into buf; call where a log line is
+     * actually emitted */
+    const char* address(char (&buf)[48]) const;
+};
+
+/*
+ * Where a synchronous reply is written. Vector mode (UDP tx arena slot,
+ * TCP scratch): the DNS message replaces the vector's content. Frame
+ * mode (balancer socket): a bsock1 REPLY frame is appended to the
+ * connection's out buffer - header first, then the message bytes - so
+ * the answer is copied exactly once, from the cache to the socket
+ * buffer.
+ */
+class ReplySink {
+  public:
+    explicit ReplySink(std::vector<uint8_t>* v) : vec_(v) {}
+    ReplySink(std::string* frames, uint32_t reqId)
+        : frames_(frames), reqId_(reqId) {}
+
+    /* start a reply of exactly dnsLen bytes (append() supplies them) */
+    void open(size_t dnsLen);
+    void append(const uint8_t* p, size_t n) {
+        if (vec_ != nullptr)
+            vec_->insert(vec_->end(), p, p + n);
+        else
+            frames_->append((const char*)p, n);
+    }
+    /* the message written so far, for in-place id/RD patching */
+    uint8_t* dns() {
+        return vec_ != nullptr ? vec_->data()
+                               : (uint8_t*)frames_->data() + start_;
+    }
+    size_t dnsLen() const {
+        return vec_ != nullptr ? vec_->size() : frames_->size() - start_;
+    }
+    /* the vector to encode into directly, or nullptr in frame mode */
+    std::vector<uint8_t>* vec() { return vec_; }
+
+  private:
+    std::vector<uint8_t>* vec_ = nullptr;
+    std::string* frames_ = nullptr;
+    uint32_t reqId_ = 0;
+    size_t start_ = 0;  /* offset of the DNS message in *frames_ */
 };
 
 class RecursionIface {
@@ -76,7 +125,7 @@ class DnsServer {
     uint64_t queriesServed() const { return served_; }
 
   private:
-    struct TcpConn {
+    struct TcpConn : std::enable_shared_from_this<TcpConn> {
         int fd;
         std::string in;
         std::string out;
@@ -86,13 +135,29 @@ class DnsServer {
         bool closed = false;
         int64_t lastActivityMs = 0;
     };
-    struct BalConn {
+    struct BalConn : std::enable_shared_from_this<BalConn> {
         int fd;
-        std::string in;
+        FrameBuf in;
         std::string out;
+        size_t outOff = 0;  /* flushed prefix of `out` (write cursor) */
         bool writeBlocked = false;
         bool closed = false;
     };
+
+    /* Where an asynchronous (recursion) reply goes. Non-owning and
+     * trivially copyable: callers fill it on the stack per query, and
+     * process() turns it into an owning closure only when the engine
+     * actually hands the query to recursion. */
+    struct ReplyTarget {
+        enum class Kind : uint8_t { Udp, Tcp, Bal } kind;
+        const struct sockaddr_storage* src = nullptr;  /* Udp */
+        socklen_t srcLen = 0;
+        TcpConn* tcp = nullptr;
+        BalConn* bal = nullptr;
+        uint32_t reqId = 0;  /* Bal */
+    };
+    std::function<void(std::vector<uint8_t>)> makeAsyncReply(
+        const ReplyTarget& t);
 
     bool openUdp();
     bool openTcp();
@@ -105,16 +170,21 @@ class DnsServer {
     void onBalConn(BalConn* c, uint32_t events);
 
     /*
-     * Decode + resolve + encode. Returns true and fills `out` when the
-     * answer is synchronous; returns false when handed to recursion (the
-     * asyncReply callback owns delivery) — or when the packet is dropped
-     * (out left empty).
+     * Decode + resolve + encode. Returns true when the answer is
+     * synchronous: it has been written to `out`, or nothing has when
+     * the packet is dropped. Returns false when handed to recursion;
+     * delivery then goes through a closure built from `target`.
      */
     bool process(const uint8_t* data, size_t len, bool udp,
-                 const ClientInfo& ci, std::vector<uint8_t>& out,
-                 std::function<void(std::vector<uint8_t>)> asyncReply);
+                 const ClientInfo& ci, ReplySink& out,
+                 const ReplyTarget& target);
     bool fastPath(const uint8_t* data, size_t len, bool udp,
-                  const ClientInfo& ci, std::vector<uint8_t>& out);
+                  const ClientInfo& ci, ReplySink& out);
+    /* "." + dnsDomain and dnsDomain + "." + datacenterName; the engine
+     * config is immutable after start, so built once */
+    std::string dotDomain_, dcSuffix_;
+    std::vector<uint8_t> encScratch_;  /* slow-path encode, frame mode */
+    std::vector<uint8_t> tcpOut_;      /* TCP sync reply scratch */
     std::string_view srvSvc_, srvProto_;   /* scratch, loop thread only */
     std::vector<uint32_t> shuffleIdx_;
     std::mt19937 rng_{std::random_device{}()};

@@ -13,9 +13,9 @@ trap 'rm -rf "$SCRATCH"' EXIT
 make BUILD="$SCRATCH/obj" \
     CXXFLAGS="-O2 -g -pg -std=c++20 -fPIC -fno-omit-frame-pointer \
               -Wall -Wextra -Wno-unused-parameter -MMD -MP" \
-    bin/binderd -j32 > /dev/null
+    bin/binderd -j16 > /dev/null
 mv bin/binderd "$SCRATCH/binderd-prof"
-make bin/binderd -j32 > /dev/null   # restore the clean binary
+make bin/binderd -j16 > /dev/null   # restore the clean binary
 
 python3 - "$SCRATCH" <<'EOF'
 import json, os, subprocess, sys, time
