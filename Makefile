@@ -113,6 +113,20 @@ $(BUILD)/framebuf_check: native/server/framebuf_check_main.cpp \
 check-framebuf: $(BUILD)/framebuf_check
 	$(BUILD)/framebuf_check 1 40
 
+# Sanitizer run of the answer table (answertab.hpp) in a stand-alone
+# program: a seeded random operation sequence against a std::unordered_map
+# model, with masked (colliding) hashes, slot growth and a small arena
+# bound that forces rebuilds. Host-only, CPU-only.
+$(BUILD)/answertab_check: native/server/answertab_check_main.cpp \
+		native/server/answertab.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-answertab: $(BUILD)/answertab_check
+	$(BUILD)/answertab_check 1 100000
+
 # release tarball layout under /opt/binder-amd (the reference ships
 # /opt/smartdc/binder with balancer+smf_adjust in lib/ and zklog in
 # bin/; Makefile:178-229 there)
@@ -138,4 +152,4 @@ clean:
 
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
-.PHONY: all clean test check check-framebuf release
+.PHONY: all clean test check check-framebuf check-answertab release

@@ -266,7 +266,10 @@ void StubStore::clearParentSvcCache(const std::string& domain) {
     size_t dot = domain.find('.');
     if (dot == std::string::npos) return;
     auto it = nodes_.find(domain.substr(dot + 1));
-    if (it != nodes_.end()) it->second->rec_.clearWireCaches();
+    if (it != nodes_.end()) {
+        it->second->rec_.clearWireCaches();
+        invalidated(it->second->domain_);
+    }
 }
 
 void StubStore::put(const std::string& domain, const Json& data) {
@@ -281,6 +284,7 @@ void StubStore::put(const std::string& domain, const Json& data) {
     if (rec.hasData) {
         n->rec_ = std::move(rec);
         reindex(n, oldAddr);
+        invalidated(d);
         clearParentSvcCache(d);
     }
 }
@@ -308,6 +312,7 @@ void StubStore::remove(const std::string& domain) {
         }
     }
     nodes_.erase(d);
+    invalidated(d);
     clearParentSvcCache(d);
 }
 

@@ -12,6 +12,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -151,6 +152,24 @@ class Store {
     }
     virtual const StoreNode* reverseLookup(const std::string& ip) const = 0;
     virtual bool ready() const = 0;
+
+    /*
+     * Invalidate hook: called with a node's domain at every place the
+     * store drops or replaces that node's fast-path caches (data or
+     * membership change, removal), and with an empty domain when the
+     * store's readiness changes ("forget everything"). binderd's
+     * answer table hangs off this; one listener is enough.
+     */
+    using InvalidateHook = std::function<void(std::string_view domain)>;
+    void setInvalidateHook(InvalidateHook h) { invalidate_ = std::move(h); }
+
+  protected:
+    void invalidated(std::string_view domain) const {
+        if (invalidate_) invalidate_(domain);
+    }
+
+  private:
+    InvalidateHook invalidate_;
 };
 
 /*
@@ -177,7 +196,10 @@ class StubStore : public Store {
     /* Set/replace a node's payload; creates intermediate parents. */
     void put(const std::string& domain, const Json& data);
     void remove(const std::string& domain);
-    void setReady(bool r) { ready_ = r; }
+    void setReady(bool r) {
+        if (r != ready_) invalidated({});
+        ready_ = r;
+    }
 
     const StoreNode* lookup(const std::string& domain) const override;
     const StoreNode* lookupView(std::string_view domain) const override;

@@ -61,6 +61,30 @@ void ReplySink::open(size_t dnsLen) {
     start_ = frames_->size();
 }
 
+uint8_t* ReplySink::openWrite(size_t dnsLen) {
+    if (vec_ != nullptr) {
+        vec_->resize(dnsLen);
+        return vec_->data();
+    }
+    constexpr size_t kHead = bsock::kHeaderLen + 4;
+    size_t at = frames_->size();
+    frames_->resize(at + kHead + dnsLen);
+    uint8_t* h = (uint8_t*)frames_->data() + at;
+    uint32_t plen = (uint32_t)(4 + dnsLen);
+    h[0] = bsock::kMagic;
+    h[1] = bsock::FRAME_REPLY;
+    h[2] = (uint8_t)plen;
+    h[3] = (uint8_t)(plen >> 8);
+    h[4] = (uint8_t)(plen >> 16);
+    h[5] = (uint8_t)(plen >> 24);
+    h[6] = (uint8_t)reqId_;
+    h[7] = (uint8_t)(reqId_ >> 8);
+    h[8] = (uint8_t)(reqId_ >> 16);
+    h[9] = (uint8_t)(reqId_ >> 24);
+    start_ = at + kHead;
+    return h + kHead;
+}
+
 DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
                      Engine* engine, Collector* collector)
     : loop_(loop), log_(std::move(log)), opts_(std::move(opts)),
@@ -89,7 +113,10 @@ DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
     txAddrs_.resize(kBatch);
 }
 
-DnsServer::~DnsServer() { stop(); }
+DnsServer::~DnsServer() {
+    stop();
+    if (engineStore_ != nullptr) engineStore_->setInvalidateHook(nullptr);
+}
 
 /* Bind a socket of the given type to opts_.host:port; v6 when the host
  * looks v6 or is empty (dual-stack any). */
@@ -401,11 +428,85 @@ static void buildServiceCache(const StoreNode* node,
     rec.svc = std::move(cache);
 }
 
+void DnsServer::setStore(Store* s) {
+    if (engineStore_ != nullptr) engineStore_->setInvalidateHook(nullptr);
+    engineStore_ = s;
+    answers_.clear();
+    if (s != nullptr)
+        s->setInvalidateHook(
+            [this](std::string_view d) { onStoreInvalidate(d); });
+}
+
+void DnsServer::onStoreInvalidate(std::string_view domain) {
+    if (domain.empty()) {  /* readiness changed: forget everything */
+        if (answers_.size() != 0) answers_.clear();
+        return;
+    }
+    if (answers_.size() == 0 || domain.size() > AnswerTable::kMaxKey)
+        return;
+    answers_.remove(AnswerTable::hashKey(domain.data(), domain.size(), 1),
+                    1, domain.data(), domain.size());
+    /* the service's SRV entry, _svc._proto.<domain>, hashed on domain */
+    answers_.removeSuffix(
+        AnswerTable::hashKey(domain.data(), domain.size(), 33), 33,
+        domain.data(), domain.size());
+}
+
+/* Write a memoised answer: copy (or permute) straight into the out
+ * buffer, patch id and RD, count it exactly as fastResolve() does. */
+void DnsServer::serveHit(const uint8_t* body, bool isSrv,
+                         const uint8_t* data, ReplySink& out) {
+    const size_t total = answerbody::total(body);
+    uint8_t* w = out.openWrite(total);
+    if (answerbody::kind(body) == answerbody::kWire) {
+        memcpy(w, answerbody::wireReply(body), total);
+    } else {
+        /* Fisher-Yates member order (server.js:40-53, 361): the same
+         * draws from rng_, in the same order, as fastResolve() */
+        size_t n = answerbody::serviceMembers(body);
+        uint8_t order[answerbody::kMaxMembers];
+        for (size_t i = 0; i < n; ++i) order[i] = (uint8_t)i;
+        for (size_t i = n; i > 1;) {
+            --i;
+            size_t j = rng_() % (i + 1);
+            std::swap(order[i], order[j]);
+        }
+        answerbody::serviceAssemble(body, order, w);
+    }
+    w[0] = data[0];
+    w[1] = data[1];
+    w[2] = (uint8_t)(w[2] | (data[2] & 0x01));
+
+    ++served_;
+    if (fpCntSrv_ == nullptr) initFastMetricSlots();
+    ++*(isSrv ? fpCntSrv_ : fpCntA_);
+    latHist_->observeFast(*(isSrv ? fpLatSrv_ : fpLatA_), 1e-6);
+    sizeHist_->observeFast(*(isSrv ? fpSizeSrv_ : fpSizeA_),
+                           (double)total);
+    BAMD_PROBE2("op-req-done", total, 0);
+}
+
 bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
                          const ClientInfo& ci, ReplySink& out) {
     /* debug/trace want the slow path's extra detail; info-level
-     * per-query lines are emitted here from cached fragments */
+     * per-query lines are emitted from cached fragments */
     if (log_.enabled(LogLevel::Debug)) return false;
+    FastQuery q;
+    if (!parseFast(data, len, q)) return false;
+    bool memo = answersOn();
+    if (memo) {
+        q.hash = answerHash(q);
+        const uint8_t* body = answers_.find(q.hash, q.isSrv ? 33 : 1,
+                                            q.name, q.nlen);
+        if (body != nullptr) {
+            serveHit(body, q.isSrv, data, out);
+            return true;
+        }
+    }
+    return fastResolve(q, data, udp, ci, out, memo);
+}
+
+bool DnsServer::parseFast(const uint8_t* data, size_t len, FastQuery& q) {
     if (len < 17 || len > 300) return false;
     /* flags: QR/opcode/AA/TC clear, RD free; byte 3 must be zero */
     if ((data[2] & 0xFE) != 0 || data[3] != 0) return false;
@@ -414,7 +515,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         data[8] | data[9] || data[10] | data[11])
         return false;
 
-    char name[256];
+    char* name = q.name;
     size_t nlen = 0;
     size_t pos = 12;
     while (true) {
@@ -422,7 +523,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         uint8_t l = data[pos++];
         if (l == 0) break;
         if ((l & 0xC0) != 0 || pos + l > len) return false;
-        if (nlen + l + 1 > sizeof(name)) return false;
+        if (nlen + l + 1 > sizeof(q.name)) return false;
         if (nlen > 0) name[nlen++] = '.';
         for (uint8_t i = 0; i < l; ++i) {
             char c = (char)data[pos + i];
@@ -444,8 +545,11 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
     if (data[pos + 2] != 0 || data[pos + 3] != 1)  /* class IN */
         return false;
 
-    std::string_view qname(name, nlen);
-    std::string_view key = qname;
+    q.nlen = (uint16_t)nlen;
+    q.isSrv = isSrv;
+    q.keyOff = 0;
+    q.svcLen = 0;
+    std::string_view key(name, nlen);
     if (isSrv) {
         /* strip _svc._proto (engine srvShape rules); mismatches fall
          * back to the slow path */
@@ -460,10 +564,24 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         if (l1.find('_', 1) != std::string_view::npos ||
             l2.find('_', 1) != std::string_view::npos)
             return false;
-        srvSvc_ = l1;
-        srvProto_ = l2;
-        key = key.substr(d2 + 1);
-        if (key.empty()) return false;
+        q.svcLen = (uint16_t)d1;
+        q.keyOff = (uint16_t)(d2 + 1);
+        if (q.keyOff >= nlen) return false;
+    }
+    return true;
+}
+
+bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
+                            bool udp, const ClientInfo& ci,
+                            ReplySink& out, bool memo) {
+    const bool isSrv = q.isSrv;
+    const char* name = q.name;
+    const size_t nlen = q.nlen;
+    const std::string_view key = q.key();
+    std::string_view srvSvc, srvProto;
+    if (isSrv) {
+        srvSvc = q.svc();
+        srvProto = q.proto();
     }
     const EngineConfig& cfg = engine_->config();
     if (!cfg.dnsDomain.empty()) {
@@ -513,7 +631,7 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
 
     if (rec.type == RecType::Service) {
         if (isSrv &&
-            (srvSvc_ != rec.srvce || srvProto_ != rec.proto))
+            (srvSvc != rec.srvce || srvProto != rec.proto))
             return false;  /* slow path: NXDOMAIN */
         if (!rec.svc) buildServiceCache(node, key, dotDomain_);
         const CompiledRecord::ServiceCache& c = *rec.svc;
@@ -593,6 +711,31 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
             log_.logRaw(LogLevel::Info, "DNS query", f);
         }
         BAMD_PROBE2("op-req-done", total, 0);
+        /* memoise: head + segments laid end to end in one blob.
+         * Replies past 512 bytes are left out, so a hit never has to
+         * ask which transport the query came over. */
+        if (memo && total <= 512 && n <= answerbody::kMaxMembers) {
+            answerbody::Seg s1[answerbody::kMaxMembers];
+            answerbody::Seg s2[answerbody::kMaxMembers];
+            size_t segBytes = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const auto& m = c.members[i];
+                if (isSrv) {
+                    s1[i] = {m.srvSeg.data(), m.srvSeg.size()};
+                    s2[i] = {m.addSeg.data(), m.addSeg.size()};
+                } else {
+                    s1[i] = {m.aSeg.data(), m.aSeg.size()};
+                    s2[i] = {nullptr, 0};
+                }
+                segBytes += s1[i].n + s2[i].n;
+            }
+            uint8_t* body = answers_.insert(
+                q.hash, (uint8_t)(isSrv ? 33 : 1), name, nlen,
+                answerbody::serviceBodyLen(n, head.size(), segBytes));
+            if (body != nullptr)
+                answerbody::serviceFill(body, n, head.data(), head.size(),
+                                        s1, s2);
+        }
         return true;
     }
 
@@ -637,6 +780,12 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
         log_.logRaw(LogLevel::Info, "DNS query", f);
     }
     BAMD_PROBE2("op-req-done", wlen, 0);
+    if (memo && wlen <= 512) {
+        uint8_t* body = answers_.insert(q.hash, 1, name, nlen,
+                                        answerbody::wireBodyLen(wlen));
+        if (body != nullptr)
+            answerbody::wireFill(body, rec.wireA.data(), wlen);
+    }
     return true;
 }
 
@@ -711,6 +860,12 @@ bool DnsServer::process(const uint8_t* data, size_t len, bool udp,
                         const ReplyTarget& target) {
     BAMD_PROBE2("op-req-start", len, (int)udp);
     if (fastPath(data, len, udp, ci, out)) return true;
+    return slowPath(data, len, udp, ci, out, target);
+}
+
+bool DnsServer::slowPath(const uint8_t* data, size_t len, bool udp,
+                         const ClientInfo& ci, ReplySink& out,
+                         const ReplyTarget& target) {
     int64_t start = nowUs();
     auto parsed = Message::decode(data, len);
     if (!parsed) return true;  // drop malformed (out empty)
@@ -1132,26 +1287,107 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
 
     /* Frames are parsed by advancing the buffer's cursor; the partial
      * frame left at the end moves to the front once, below. */
-    bsock::FrameView fr;
-    bsock::FrameStatus st;
-    while ((st = bsock::nextFrame(c->in, fr)) == bsock::FrameStatus::Ok) {
-        if (fr.type == bsock::FRAME_PING) {
-            bsock::appendFrame(c->out, bsock::FRAME_PONG, "");
-        } else if (fr.type == bsock::FRAME_QUERY) {
-            bsock::QueryFrame qf;
-            if (bsock::parseQuery(fr.payload, fr.plen, qf)) {
-                ClientInfo ci;
-                ci.family = qf.proto == 1 ? "tcp" : "udp";
-                ci.port = qf.srcPort;
-                ci.ipFamily = qf.family == 4 ? 4 : 6;
-                memcpy(ci.addr, qf.srcAddr, sizeof(ci.addr));
-                ReplySink sink(&c->out, qf.reqId);
-                ReplyTarget target{ReplyTarget::Kind::Bal};
-                target.bal = c;
-                target.reqId = qf.reqId;
-                process(qf.dns, qf.dnsLen, qf.proto == 0, ci, sink,
-                        target);
+    /*
+     * The frames of this read are served through a short software
+     * pipeline: the per-query cost at saturation is cache misses on
+     * the answer table, and the addresses are known as soon as a
+     * frame's name has been parsed. Frame i+kPipeDepth is parsed,
+     * hashed and its slot prefetched; frame i+kPipeBlobLead has its
+     * slot read and its blob prefetched; frame i is then served from
+     * lines already on their way. Frames are served strictly in
+     * arrival order, so replies leave in the order they do without
+     * the pipeline; PINGs, queries the fast path does not take and
+     * table misses go through the usual code at their place in that
+     * order. With the table bypassed (info/debug logging) nothing is
+     * parsed ahead.
+     */
+    enum : uint8_t { kSkip, kPing, kQuery, kFastQuery };
+    struct PipeFrame {
+        uint8_t kind;
+        bsock::QueryFrame qf;
+        FastQuery q;
+        uint32_t off;   /* probe() result, good while gen matches */
+        uint64_t gen;
+    };
+    static_assert((kPipeDepth & (kPipeDepth - 1)) == 0 &&
+                  kPipeBlobLead >= 1 && kPipeBlobLead <= kPipeDepth);
+    PipeFrame ring[kPipeDepth];
+    const bool memo = answersOn() && engineStore_ != nullptr;
+    bsock::FrameStatus st = bsock::FrameStatus::Ok;
+    size_t fetched = 0, probed = 0, served = 0;
+    while (true) {
+        /* stage 1: take frames off the buffer, up to the lookahead */
+        while (st == bsock::FrameStatus::Ok &&
+               fetched - served < kPipeDepth) {
+            bsock::FrameView fr;
+            st = bsock::nextFrame(c->in, fr);
+            if (st != bsock::FrameStatus::Ok) break;
+            PipeFrame& p = ring[fetched++ & (kPipeDepth - 1)];
+            p.off = AnswerTable::kNone;
+            if (fr.type == bsock::FRAME_PING) {
+                p.kind = kPing;
+            } else if (fr.type == bsock::FRAME_QUERY &&
+                       bsock::parseQuery(fr.payload, fr.plen, p.qf)) {
+                p.kind = kQuery;
+                if (memo && parseFast(p.qf.dns, p.qf.dnsLen, p.q)) {
+                    p.kind = kFastQuery;
+                    p.q.hash = answerHash(p.q);
+                    answers_.prefetchSlot(p.q.hash);
+                }
+            } else {
+                p.kind = kSkip;
             }
+        }
+        if (served == fetched) break;
+        /* stage 2: slot -> blob address, blob lines requested */
+        while (probed < fetched && probed - served < kPipeBlobLead) {
+            PipeFrame& p = ring[probed++ & (kPipeDepth - 1)];
+            if (p.kind != kFastQuery) continue;
+            uint32_t blen = 0;
+            p.off = answers_.probe(p.q.hash, &blen);
+            p.gen = answers_.generation();
+            if (p.off != AnswerTable::kNone)
+                answers_.prefetchBlob(p.off, blen);
+        }
+        /* stage 3: serve the oldest frame */
+        PipeFrame& p = ring[served++ & (kPipeDepth - 1)];
+        if (p.kind == kPing) {
+            bsock::appendFrame(c->out, bsock::FRAME_PONG, "");
+            continue;
+        }
+        if (p.kind == kSkip) continue;
+        const bsock::QueryFrame& qf = p.qf;
+        ReplySink sink(&c->out, qf.reqId);
+        const bool udp = qf.proto == 0;
+        if (p.kind == kFastQuery) {
+            const uint8_t qt = p.q.isSrv ? 33 : 1;
+            const uint8_t* body = nullptr;
+            if (p.off != AnswerTable::kNone &&
+                p.gen == answers_.generation())
+                body = answers_.at(p.off, qt, p.q.name, p.q.nlen);
+            if (body == nullptr)  /* not probed, stale, or a collision */
+                body = answers_.find(p.q.hash, qt, p.q.name, p.q.nlen);
+            if (body != nullptr) {
+                BAMD_PROBE2("op-req-start", qf.dnsLen, (int)udp);
+                serveHit(body, p.q.isSrv, qf.dns, sink);
+                continue;
+            }
+        }
+        ClientInfo ci;
+        ci.family = qf.proto == 1 ? "tcp" : "udp";
+        ci.port = qf.srcPort;
+        ci.ipFamily = qf.family == 4 ? 4 : 6;
+        memcpy(ci.addr, qf.srcAddr, sizeof(ci.addr));
+        ReplyTarget target{ReplyTarget::Kind::Bal};
+        target.bal = c;
+        target.reqId = qf.reqId;
+        if (p.kind == kFastQuery) {
+            /* table miss: the fast path proper, from the parse at hand */
+            BAMD_PROBE2("op-req-start", qf.dnsLen, (int)udp);
+            if (!fastResolve(p.q, qf.dns, udp, ci, sink, true))
+                slowPath(qf.dns, qf.dnsLen, udp, ci, sink, target);
+        } else {
+            process(qf.dns, qf.dnsLen, udp, ci, sink, target);
         }
     }
     if (st == bsock::FrameStatus::Bad) {

@@ -28,6 +28,7 @@
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
 #include "../engine/engine.hpp"
+#include "answertab.hpp"
 #include "framebuf.hpp"
 #include "metrics.hpp"
 
@@ -76,6 +77,9 @@ class ReplySink {
 
     /* start a reply of exactly dnsLen bytes (append() supplies them) */
     void open(size_t dnsLen);
+    /* start a reply of exactly dnsLen bytes and return where to write
+     * them: the caller fills the message in place, no append() */
+    uint8_t* openWrite(size_t dnsLen);
     void append(const uint8_t* p, size_t n) {
         if (vec_ != nullptr)
             vec_->insert(vec_->end(), p, p + n);
@@ -180,12 +184,69 @@ class DnsServer {
                  const ReplyTarget& target);
     bool fastPath(const uint8_t* data, size_t len, bool udp,
                   const ClientInfo& ci, ReplySink& out);
+    /* The rest of process() once fastPath() has declined. */
+    bool slowPath(const uint8_t* data, size_t len, bool udp,
+                  const ClientInfo& ci, ReplySink& out,
+                  const ReplyTarget& target);
+
+    /* A query the fast path may serve: header and question checked,
+     * name lowercase [a-z0-9_-] labels in dotted form. For SRV the
+     * store key is the name behind the _svc._proto labels. */
+    struct FastQuery {
+        char name[256];
+        uint16_t nlen = 0;
+        uint16_t keyOff = 0;  /* SRV: where the service's domain starts */
+        uint16_t svcLen = 0;  /* SRV: length of the _svc label */
+        bool isSrv = false;
+        uint64_t hash = 0;    /* answer-table hash, see answerHash() */
+
+        std::string_view qname() const { return {name, nlen}; }
+        std::string_view key() const {
+            return {name + keyOff, (size_t)(nlen - keyOff)};
+        }
+        std::string_view svc() const { return {name, svcLen}; }
+        std::string_view proto() const {
+            return {name + svcLen + 1, (size_t)(keyOff - svcLen - 2)};
+        }
+    };
+    static bool parseFast(const uint8_t* data, size_t len, FastQuery& q);
+    /* policy checks + store lookup + cached-record serve (the fast
+     * path proper); memoises what it served when `memo` is set */
+    bool fastResolve(const FastQuery& q, const uint8_t* data, bool udp,
+                     const ClientInfo& ci, ReplySink& out, bool memo);
+    /* serve a memoised answer body (answerbody:: layouts) */
+    void serveHit(const uint8_t* body, bool isSrv, const uint8_t* data,
+                  ReplySink& out);
+    /* info and debug levels bypass the answer table: their per-query
+     * log lines are built from the records, not from the memo */
+    bool answersOn() const { return !log_.enabled(LogLevel::Info); }
+    void onStoreInvalidate(std::string_view domain);
+
+    /*
+     * Answer table: memo of fastResolve()'s replies, (qname, qtype) ->
+     * finished bytes. Inserted only by fastResolve(); dropped per name
+     * through the store's invalidate hook, wholesale when the store's
+     * readiness changes. An SRV entry is hashed on the service's
+     * domain (the A entry on the whole name) so both can be found from
+     * the domain alone.
+     */
+    AnswerTable answers_;
+    static uint64_t answerHash(const FastQuery& q) {
+        return q.isSrv ? AnswerTable::hashKey(q.name + q.keyOff,
+                                              q.nlen - q.keyOff, 33)
+                       : AnswerTable::hashKey(q.name, q.nlen, 1);
+    }
+    /* onBalConn software pipeline: a frame is parsed, hashed and its
+     * table slot prefetched kPipeDepth frames before it is served,
+     * and its blob prefetched kPipeBlobLead frames before. Measured
+     * with bsockblast on the bench tree (profiles/SCALING.md). */
+    static constexpr size_t kPipeDepth = 8;
+    static constexpr size_t kPipeBlobLead = 4;
     /* "." + dnsDomain and dnsDomain + "." + datacenterName; the engine
      * config is immutable after start, so built once */
     std::string dotDomain_, dcSuffix_;
     std::vector<uint8_t> encScratch_;  /* slow-path encode, frame mode */
     std::vector<uint8_t> tcpOut_;      /* TCP sync reply scratch */
-    std::string_view srvSvc_, srvProto_;   /* scratch, loop thread only */
     std::vector<uint32_t> shuffleIdx_;
     std::mt19937 rng_{std::random_device{}()};
     void initFastMetricSlots();
@@ -200,10 +261,10 @@ class DnsServer {
 
   public:
     /* the store behind the engine (fast-path lookups); set by main */
-    void setStore(const Store* s) { engineStore_ = s; }
+    void setStore(Store* s);
 
   private:
-    const Store* engineStore_ = nullptr;
+    Store* engineStore_ = nullptr;
 
     void afterQuery(const dns::Message& query, const dns::Message& resp,
                     const QueryResult& qr, const ClientInfo& ci,

@@ -73,7 +73,7 @@ const StoreNode* ZkMirror::reverseLookup(const std::string& ip) const {
 bool ZkMirror::ready() const {
     /* true once the root node object exists, i.e. after the first
      * session event — even before data lands (zk.js:55-58). */
-    return byDomain_.count(opts_.domain) > 0;
+    return ready_;
 }
 
 ZkMirror::Node* ZkMirror::nodeAt(const std::string& path) {
@@ -88,6 +88,9 @@ void ZkMirror::rebuild() {
         root_ = n.get();
         byDomain_[root_->domain_] = root_;
         byPath_[root_->path_] = std::move(n);
+        /* same test the per-query lookup used to make */
+        ready_ = byDomain_.count(opts_.domain) > 0;
+        invalidated({});
     }
     /* Re-bind the whole existing tree with fresh reads+watches. */
     std::vector<Node*> stack{root_};
@@ -171,6 +174,7 @@ void ZkMirror::onChildren(const std::string& path,
              * under distinct paths, but guard like zk.js:205-207). */
             byDomain_[raw->domain_] = raw;
             byPath_[raw->path_] = std::move(node);
+            invalidated(raw->domain_);
             newKids[kid] = raw;
             bind(raw);
         }
@@ -179,6 +183,7 @@ void ZkMirror::onChildren(const std::string& path,
     for (auto& [label, old] : n->kids_) unbind(old);
     n->kids_ = std::move(newKids);
     n->rec_.clearWireCaches();  /* membership feeds service responses */
+    invalidated(n->domain_);
 }
 
 void ZkMirror::unbind(Node* n) {
@@ -190,6 +195,12 @@ void ZkMirror::unbind(Node* n) {
     }
     auto dit = byDomain_.find(n->domain_);
     if (dit != byDomain_.end() && dit->second == n) byDomain_.erase(dit);
+    invalidated(n->domain_);
+    bool nowReady = byDomain_.count(opts_.domain) > 0;
+    if (nowReady != ready_) {
+        ready_ = nowReady;
+        invalidated({});
+    }
     byPath_.erase(n->path_);  // frees n
 }
 
@@ -222,11 +233,15 @@ void ZkMirror::onData(const std::string& path, const std::string& data) {
         n->ip_ = newIp;
     }
     n->rec_ = std::move(rec);
+    invalidated(n->domain_);
     /* member data feeds the parent's cached service responses */
     size_t slash = path.rfind('/');
     if (slash != std::string::npos && slash > 0) {
         Node* parent = nodeAt(path.substr(0, slash));
-        if (parent != nullptr) parent->rec_.clearWireCaches();
+        if (parent != nullptr) {
+            parent->rec_.clearWireCaches();
+            invalidated(parent->domain_);
+        }
     }
 }
 

@@ -88,6 +88,9 @@ class ZkMirror : public Store {
     std::unordered_map<std::string, Node*, SvHash, SvEq> byDomain_;
     std::unordered_map<std::string, Node*> rev_;
     Node* root_ = nullptr;
+    /* ready() is asked per query: a flag kept where the root node is
+     * created or removed, not a hash lookup of the root's domain */
+    bool ready_ = false;
 
     Counter* nodesGauge_ = nullptr;
     Counter* sessionsCounter_ = nullptr;
