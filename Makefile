@@ -127,6 +127,28 @@ $(BUILD)/answertab_check: native/server/answertab_check_main.cpp \
 check-answertab: $(BUILD)/answertab_check
 	$(BUILD)/answertab_check 1 100000
 
+# ThreadSanitizer run of the serving-thread pool: binderd itself (a daemon
+# with its own main) built with -fsanitize=thread into $(BUILD)/tsan, and
+# the pool's tests plus the two suites that pin reply order and ingress
+# run against it. The tests fail on any ThreadSanitizer report in a
+# daemon's log. Host-only, CPU-only.
+TSAN_FLAGS := -O1 -g -std=c++20 -fsanitize=thread -fno-omit-frame-pointer \
+	-Wall -Wextra -Werror -Wno-unused-parameter
+TSAN_SRCS := $(CORE_SRCS) $(SERVER_SRCS) native/server/binderd_main.cpp
+TSAN_OBJS := $(TSAN_SRCS:%.cpp=$(BUILD)/tsan/obj/%.o)
+
+$(BUILD)/tsan/obj/%.o: %.cpp
+	@mkdir -p $(dir $@)
+	$(CXX) $(TSAN_FLAGS) -MMD -MP -c $< -o $@
+
+$(BUILD)/tsan/binderd: $(TSAN_OBJS)
+	$(CXX) $(TSAN_FLAGS) $^ -o $@ -lssl -lcrypto -lpthread
+
+check-serve-threads: all $(BUILD)/tsan/binderd
+	BINDERD_BIN=$(CURDIR)/$(BUILD)/tsan/binderd $(PYTHON) -m pytest -q \
+	    tests/test_serve_threads.py tests/test_answer_table.py \
+	    tests/test_bsock_ingress.py
+
 # release tarball layout under /opt/binder-amd (the reference ships
 # /opt/smartdc/binder with balancer+smf_adjust in lib/ and zklog in
 # bin/; Makefile:178-229 there)
@@ -152,4 +174,5 @@ clean:
 
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
-.PHONY: all clean test check check-framebuf check-answertab release
+.PHONY: all clean test check check-framebuf check-answertab \
+	check-serve-threads release

@@ -50,6 +50,10 @@ void EventLoop::postFromThread(TimerCallback cb) {
         std::lock_guard<std::mutex> g(postMutex_);
         posted_.push_back(std::move(cb));
     }
+    wake();
+}
+
+void EventLoop::wake() {
     uint64_t one = 1;
     ssize_t rv = write(wakeFd_, &one, sizeof(one));
     (void)rv;
@@ -64,6 +68,7 @@ void EventLoop::addFd(int fd, uint32_t events, FdCallback cb) {
         throw std::runtime_error(std::string("epoll_ctl add: ") +
                                  strerror(errno));
     fds_[fd] = FdReg{gen, std::move(cb)};
+    wakeIfForeign();
 }
 
 void EventLoop::modFd(int fd, uint32_t events) {
@@ -86,12 +91,16 @@ uint64_t EventLoop::addTimer(int64_t delayMs, TimerCallback cb) {
     uint64_t id = nextTimerId_++;
     timers_[id] = std::move(cb);
     heap_.push(Timer{monotonicMillis() + delayMs, id});
+    wakeIfForeign();
     return id;
 }
 
 void EventLoop::cancelTimer(uint64_t id) { timers_.erase(id); }
 
-void EventLoop::defer(TimerCallback cb) { deferred_.push_back(std::move(cb)); }
+void EventLoop::defer(TimerCallback cb) {
+    deferred_.push_back(std::move(cb));
+    wakeIfForeign();
+}
 
 int64_t EventLoop::nextTimerDelay() const {
     if (!deferred_.empty()) return 0;
@@ -114,6 +123,10 @@ void EventLoop::fireTimers() {
 }
 
 void EventLoop::runOnce(int64_t maxWaitMs) {
+    /* with a dispatch lock: held for everything but the wait */
+    std::unique_lock<std::mutex> lk;
+    if (dispatchLock_ != nullptr)
+        lk = std::unique_lock<std::mutex>(*dispatchLock_);
     // Run deferred tasks queued before this iteration.
     if (!deferred_.empty()) {
         std::vector<TimerCallback> tasks;
@@ -125,7 +138,11 @@ void EventLoop::runOnce(int64_t maxWaitMs) {
     if (wait < 0 || wait > maxWaitMs) wait = maxWaitMs;
 
     struct epoll_event evs[64];
+    if (lk.owns_lock()) lk.unlock();
     int n = epoll_wait(epfd_, evs, 64, (int)wait);
+    int waitErrno = errno;
+    if (dispatchLock_ != nullptr) lk.lock();
+    errno = waitErrno;
     if (n < 0) {
         if (errno == EINTR) return;
         throw std::runtime_error(std::string("epoll_wait: ") +
@@ -145,6 +162,7 @@ void EventLoop::runOnce(int64_t maxWaitMs) {
 }
 
 void EventLoop::run() {
+    loopThread_.store(std::this_thread::get_id(), std::memory_order_relaxed);
     running_ = true;
     while (running_) runOnce(1000);
 }
@@ -152,6 +170,7 @@ void EventLoop::run() {
 bool EventLoop::runUntil(const std::function<bool()>& pred,
                          int64_t timeoutMs) {
     int64_t deadline = monotonicMillis() + timeoutMs;
+    loopThread_.store(std::this_thread::get_id(), std::memory_order_relaxed);
     running_ = true;
     while (running_) {
         if (pred()) return true;

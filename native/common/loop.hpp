@@ -5,6 +5,18 @@
  * SURVEY.md §3.1 "no worker threads"). We keep the same concurrency model —
  * one loop per process, N processes behind the balancer for scale-out — but
  * on raw epoll with edge-level callbacks and a timer heap.
+ *
+ * Threads. A loop belongs to the thread that calls run()/runUntil():
+ *  - postFromThread() and stop() are legal from any thread, always;
+ *  - everything else (addFd, modFd, delFd, addTimer, cancelTimer, defer)
+ *    is legal from the loop thread, from its callbacks;
+ *  - on a loop with a dispatch lock (setDispatchLock), the same calls are
+ *    also legal from another thread *while that thread holds the lock*.
+ *    The loop holds the lock whenever it runs callbacks, timers or
+ *    deferred tasks and drops it only around epoll_wait, so the lock
+ *    holder has the loop's tables to itself. addFd, addTimer and defer
+ *    made that way wake the loop, so a new timer deadline or deferred
+ *    task is seen at once instead of after the current wait.
  */
 #pragma once
 
@@ -14,6 +26,7 @@
 #include <map>
 #include <mutex>
 #include <queue>
+#include <thread>
 #include <vector>
 
 namespace bamd {
@@ -51,8 +64,23 @@ class EventLoop {
     /* Run until pred() is true or timeout; for tests/clients. */
     bool runUntil(const std::function<bool()>& pred, int64_t timeoutMs);
 
+    /* Optional dispatch lock, see "Threads" above. Set before run();
+     * the mutex outlives the loop's last iteration. */
+    void setDispatchLock(std::mutex* m) { dispatchLock_ = m; }
+
+    /* True on the thread that is running this loop. */
+    bool inLoopThread() const {
+        return loopThread_.load(std::memory_order_relaxed) ==
+               std::this_thread::get_id();
+    }
+
   private:
     void runOnce(int64_t maxWaitMs);
+    void wake();
+    /* a registration made under the dispatch lock by another thread */
+    void wakeIfForeign() {
+        if (dispatchLock_ != nullptr && !inLoopThread()) wake();
+    }
     int64_t nextTimerDelay() const;
     void fireTimers();
 
@@ -84,6 +112,8 @@ class EventLoop {
     std::vector<TimerCallback> deferred_;
 
     int wakeFd_ = -1;
+    std::mutex* dispatchLock_ = nullptr;
+    std::atomic<std::thread::id> loopThread_{};
     std::mutex postMutex_;
     std::vector<TimerCallback> posted_;
 };

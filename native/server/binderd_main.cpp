@@ -12,7 +12,9 @@
  * plus binder-amd extensions:
  *   -S <mode>  store mode: "zk" (default) or "file:<path>" (static JSON
  *              tree, used by tests/bench config 1)
- * Env: ZK_HOST (lib/zk.js:34), ZK_PORT (test/helper.js:54), LOG_LEVEL.
+ * Env: ZK_HOST (lib/zk.js:34), ZK_PORT (test/helper.js:54), LOG_LEVEL,
+ * BINDER_SERVE_THREADS (overrides config key serveThreads; threads that
+ * serve balancer connections, 1 = the main thread alone).
  * Option precedence: defaults < config file < CLI (main.js:105).
  * Metrics HTTP on port+1000 (main.js:144-152).
  */
@@ -202,6 +204,13 @@ int main(int argc, char** argv) {
     sopts.host = opts.get("host").asString();
     sopts.port = port;
     sopts.balancerSocket = opts.get("balancerSocket").asString();
+    sopts.serveThreads = defaultServeThreads();
+    if (opts.get("serveThreads").isNumber())
+        sopts.serveThreads = (int)opts.get("serveThreads").asInt();
+    if (const char* st = getenv("BINDER_SERVE_THREADS"); st && *st)
+        sopts.serveThreads = atoi(st);
+    if (sopts.serveThreads < 1) sopts.serveThreads = 1;
+    if (sopts.serveThreads > 64) sopts.serveThreads = 64;
 
     DnsServer server(&loop, log, sopts, &engine, &collector);
     server.setStore(store);
@@ -226,14 +235,9 @@ int main(int argc, char** argv) {
         server.setRecursion(recursion.get());
     }
 
-    if (!server.start()) {
-        log.fatal("error initing binder");
-        return 1;
-    }
-    log.info("done with binder init");
-
     /* SIGTERM: unlink balancer socket then exit (main.js:181-193);
-     * SIGINT for interactive use. */
+     * SIGINT for interactive use. Blocked before start() so that the
+     * serving threads inherit the mask and the signalfd gets them. */
     sigset_t mask;
     sigemptyset(&mask);
     sigaddset(&mask, SIGTERM);
@@ -251,6 +255,12 @@ int main(int argc, char** argv) {
         }
         loop.stop();
     });
+
+    if (!server.start()) {
+        log.fatal("error initing binder");
+        return 1;
+    }
+    log.info("done with binder init");
 
     loop.run();
     server.stop();

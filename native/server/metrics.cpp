@@ -9,18 +9,41 @@
 
 #include <cstdio>
 #include <cstring>
+#include <stdexcept>
 
 namespace bamd {
 
 Histogram::Histogram()
     : bounds_({0.0001, 0.00025, 0.0005, 0.001, 0.0025, 0.005, 0.01, 0.025,
-               0.05, 0.1, 0.25, 0.5, 1, 2.5, 5, 10}) {}
+               0.05, 0.1, 0.25, 0.5, 1, 2.5, 5, 10}) {
+    if (bounds_.size() + 1 != kBuckets)
+        throw std::logic_error("Histogram::kBuckets out of step");
+}
 
 Histogram::Series& Histogram::seriesRef(const std::string& labels) {
     Series& s = series_[labels];
     if (s.bucketCounts.empty())
         s.bucketCounts.resize(bounds_.size() + 1, 0);
     return s;
+}
+
+void Histogram::fold(const std::string& labels, const Shard& s, Fold& f) {
+    constexpr auto rx = std::memory_order_relaxed;
+    /* count first: a writer in mid-observation then shows as buckets
+     * ahead of count, never as a count no bucket holds */
+    uint64_t count = s.count.load(rx);
+    if (count == f.count) return;
+    Series& dst = seriesRef(labels);
+    for (size_t i = 0; i < kBuckets && i < dst.bucketCounts.size(); ++i) {
+        uint64_t b = s.buckets[i].load(rx);
+        dst.bucketCounts[i] += b - f.buckets[i];
+        f.buckets[i] = b;
+    }
+    double sum = s.sum.load(rx);
+    dst.sum += sum - f.sum;
+    f.sum = sum;
+    dst.count += count - f.count;
+    f.count = count;
 }
 
 void Histogram::observe(const std::string& labels, double v) {
@@ -76,6 +99,7 @@ static void appendLabelSet(std::string& out, const std::string& a,
 }
 
 std::string Collector::expose(const std::string& staticLabels) const {
+    if (beforeExpose_) beforeExpose_();
     std::string out;
     out.reserve(4096);
     char buf[64];

@@ -9,7 +9,9 @@
  */
 #pragma once
 
+#include <atomic>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -18,6 +20,27 @@
 #include "../common/loop.hpp"
 
 namespace bamd {
+
+/*
+ * Shards: the hit path's counters, one set per serving context. A shard
+ * has one writer (the context's thread) that uses relaxed loads and
+ * stores - no locked instruction, no line shared with another writer -
+ * and is read by whoever renders a scrape, which folds what the shard
+ * gained since the last scrape into the labelled value below. The
+ * folded-so-far figures (CounterFold, Histogram::Fold) belong to the
+ * scraping side alone.
+ */
+struct CounterShard {
+    std::atomic<uint64_t> v{0};
+    void bump() {
+        v.store(v.load(std::memory_order_relaxed) + 1,
+                std::memory_order_relaxed);
+    }
+    uint64_t read() const { return v.load(std::memory_order_relaxed); }
+};
+struct CounterFold {
+    uint64_t seen = 0;
+};
 
 class Counter {
   public:
@@ -31,6 +54,12 @@ class Counter {
         vals_[labels] = v;
     }
     const std::map<std::string, uint64_t>& values() const { return vals_; }
+    void fold(const std::string& labels, const CounterShard& s,
+              CounterFold& f) {
+        uint64_t now = s.read();
+        if (now != f.seen) vals_[labels] += now - f.seen;
+        f.seen = now;
+    }
 
   private:
     std::map<std::string, uint64_t> vals_;
@@ -58,6 +87,28 @@ class Histogram {
         double sum = 0;
         uint64_t count = 0;
     };
+
+    /* one series' shard; see CounterShard */
+    static constexpr size_t kBuckets = 17;  /* bounds + the +Inf bucket */
+    struct Shard {
+        std::atomic<uint64_t> buckets[kBuckets] = {};
+        std::atomic<double> sum{0};
+        std::atomic<uint64_t> count{0};
+    };
+    struct Fold {
+        uint64_t buckets[kBuckets] = {};
+        double sum = 0;
+        uint64_t count = 0;
+    };
+    void observeShard(Shard& s, double v) const {
+        constexpr auto rx = std::memory_order_relaxed;
+        size_t i = 0;
+        while (i < bounds_.size() && v > bounds_[i]) ++i;
+        s.buckets[i].store(s.buckets[i].load(rx) + 1, rx);
+        s.sum.store(s.sum.load(rx) + v, rx);
+        s.count.store(s.count.load(rx) + 1, rx);
+    }
+    void fold(const std::string& labels, const Shard& s, Fold& f);
     const std::vector<double>& bounds() const { return bounds_; }
     const std::map<std::string, Series>& series() const { return series_; }
 
@@ -76,6 +127,11 @@ class Collector {
      * 'k="v",k2="v2"' (may be empty). */
     std::string expose(const std::string& staticLabels) const;
 
+    /* run at the start of every expose(): folds shards in */
+    void setBeforeExpose(std::function<void()> f) {
+        beforeExpose_ = std::move(f);
+    }
+
   private:
     struct Metric {
         std::string name, help, kind;
@@ -83,6 +139,7 @@ class Collector {
         std::unique_ptr<Histogram> histogram;
     };
     std::vector<Metric> metrics_;
+    std::function<void()> beforeExpose_;
 };
 
 /*

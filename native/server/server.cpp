@@ -1,11 +1,14 @@
 #include "server.hpp"
 
 #include <arpa/inet.h>
+#include <sched.h>
 #include <sys/epoll.h>
 #include <unistd.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <fstream>
 
 #include "../balancer/protocol.hpp"
 #include "../common/probes.hpp"
@@ -88,7 +91,9 @@ uint8_t* ReplySink::openWrite(size_t dnsLen) {
 DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
                      Engine* engine, Collector* collector)
     : loop_(loop), log_(std::move(log)), opts_(std::move(opts)),
-      engine_(engine) {
+      engine_(engine), collector_(collector) {
+    main_.loop = loop_;
+    collector_->setBeforeExpose([this]() { foldShards(); });
     /* Metric names/help strings match the reference
      * (lib/server.js:31-34, 456-469). */
     reqCounter_ = collector->counter("binder_requests_completed",
@@ -115,6 +120,7 @@ DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
 
 DnsServer::~DnsServer() {
     stop();
+    collector_->setBeforeExpose(nullptr);
     if (engineStore_ != nullptr) engineStore_->setInvalidateHook(nullptr);
 }
 
@@ -233,9 +239,61 @@ bool DnsServer::openBalancer() {
     return true;
 }
 
+/* whole CPUs this process may use: cgroup quota (v2, then v1), capped
+ * by the affinity mask; the affinity mask alone when there is no quota */
+static int usableCpus() {
+    int cpus = 0;
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof(set), &set) == 0)
+        cpus = CPU_COUNT(&set);
+    if (cpus < 1) cpus = 1;
+    long long quota = -1, period = 0;
+    {
+        std::ifstream f("/sys/fs/cgroup/cpu.max");
+        std::string q;
+        if (f >> q >> period && q != "max") quota = atoll(q.c_str());
+    }
+    if (quota <= 0) {
+        std::ifstream fq("/sys/fs/cgroup/cpu/cpu.cfs_quota_us");
+        std::ifstream fp("/sys/fs/cgroup/cpu/cpu.cfs_period_us");
+        if (!(fq >> quota) || !(fp >> period)) quota = -1;
+    }
+    if (quota > 0 && period > 0) {
+        long long q = quota / period;
+        if (q < 1) q = 1;
+        if (q < cpus) cpus = (int)q;
+    }
+    return cpus;
+}
+
+int defaultServeThreads() {
+    int t = usableCpus() / 4;
+    return t < 1 ? 1 : (t > 4 ? 4 : t);
+}
+
+bool DnsServer::pooled() const {
+    return opts_.serveThreads >= 2 && !opts_.balancerSocket.empty() &&
+           answersOn();
+}
+
 bool DnsServer::start() {
     if (!openUdp() || !openTcp()) return false;
     if (!opts_.balancerSocket.empty() && !openBalancer()) return false;
+    if (pooled()) {
+        /* from here on the main loop dispatches under the serving lock */
+        loop_->setDispatchLock(&serveMu_);
+        for (int i = 0; i < opts_.serveThreads; ++i) {
+            auto ctx = std::make_unique<ServeCtx>();
+            ctx->pooled = true;
+            ctx->ownLoop = std::make_unique<EventLoop>();
+            ctx->loop = ctx->ownLoop.get();
+            EventLoop* l = ctx->loop;
+            ctx->thread = std::thread([l]() { l->run(); });
+            pool_.push_back(std::move(ctx));
+        }
+        log_.info({{"threads", Json((int64_t)opts_.serveThreads)}},
+                  "balancer connections served by a thread pool");
+    }
     /* idle TCP sweep: DNS-over-TCP clients that neither query nor
      * close get reaped after 60s (resource protection; the balancer
      * socket is exempt — it is a long-lived peer) */
@@ -257,7 +315,29 @@ void DnsServer::sweepIdleTcp() {
     for (TcpConn* c : idle) closeTcp(c);
 }
 
+/* Stop and join the pool. Not to be called with the serving lock held:
+ * a pool thread may be waiting for it. */
+void DnsServer::stopPool() {
+    for (auto& ctx : pool_) {
+        EventLoop* l = ctx->loop;
+        /* stopped from inside, so a thread that has not reached run()
+         * yet still sees it */
+        l->postFromThread([l]() { l->stop(); });
+    }
+    for (auto& ctx : pool_)
+        if (ctx->thread.joinable()) ctx->thread.join();
+    /* the threads are gone: their connections are ours to close */
+    for (auto& ctx : pool_) {
+        for (auto& [fd, c] : ctx->balConns) {
+            c->closed = true;
+            close(fd);
+        }
+        ctx->balConns.clear();
+    }
+}
+
 void DnsServer::stop() {
+    stopPool();
     auto closeFd = [this](int& fd) {
         if (fd >= 0) {
             loop_->delFd(fd);
@@ -274,11 +354,21 @@ void DnsServer::stop() {
         close(fd);
     }
     tcpConns_.clear();
-    for (auto& [fd, c] : balConns_) {
+    for (auto& [fd, c] : main_.balConns) {
         loop_->delFd(fd);
         close(fd);
     }
-    balConns_.clear();
+    main_.balConns.clear();
+}
+
+uint64_t DnsServer::queriesServed() const {
+    uint64_t n = servedSlow_;
+    auto add = [&n](const ServeCtx& c) {
+        n += c.hits.cntA.read() + c.hits.cntSrv.read();
+    };
+    add(main_);
+    for (const auto& c : pool_) add(*c);
+    return n;
 }
 
 /* ---------------- query pipeline ---------------- */
@@ -431,30 +521,107 @@ static void buildServiceCache(const StoreNode* node,
 void DnsServer::setStore(Store* s) {
     if (engineStore_ != nullptr) engineStore_->setInvalidateHook(nullptr);
     engineStore_ = s;
-    answers_.clear();
+    main_.answers.clear();
     if (s != nullptr)
         s->setInvalidateHook(
             [this](std::string_view d) { onStoreInvalidate(d); });
 }
 
+/* The store's hook: main thread, serving lock held when a pool runs.
+ * Returns only once every pool thread's inbox holds the invalidation,
+ * which is what makes a mutation visible everywhere before any fresh
+ * answer can be built from it (docs/ARCHITECTURE.md). */
 void DnsServer::onStoreInvalidate(std::string_view domain) {
+    applyInvalidate(main_.answers, domain);
+    for (auto& ctx : pool_) postInvalidate(*ctx, domain);
+}
+
+void DnsServer::applyInvalidate(AnswerTable& answers,
+                                std::string_view domain) {
     if (domain.empty()) {  /* readiness changed: forget everything */
-        if (answers_.size() != 0) answers_.clear();
+        if (answers.size() != 0) answers.clear();
         return;
     }
-    if (answers_.size() == 0 || domain.size() > AnswerTable::kMaxKey)
+    if (answers.size() == 0 || domain.size() > AnswerTable::kMaxKey)
         return;
-    answers_.remove(AnswerTable::hashKey(domain.data(), domain.size(), 1),
-                    1, domain.data(), domain.size());
+    answers.remove(AnswerTable::hashKey(domain.data(), domain.size(), 1),
+                   1, domain.data(), domain.size());
     /* the service's SRV entry, _svc._proto.<domain>, hashed on domain */
-    answers_.removeSuffix(
+    answers.removeSuffix(
         AnswerTable::hashKey(domain.data(), domain.size(), 33), 33,
         domain.data(), domain.size());
 }
 
+void DnsServer::postInvalidate(ServeCtx& ctx, std::string_view domain) {
+    std::lock_guard<std::mutex> g(ctx.inboxMu);
+    bool clearPending = ctx.inbox.size() == 1 && ctx.inbox[0].empty();
+    if (domain.empty() || ctx.inbox.size() >= kInboxMax) {
+        /* an idle thread never drains: bound what it is owed */
+        ctx.inbox.clear();
+        ctx.inbox.emplace_back();
+    } else if (!clearPending) {
+        ctx.inbox.emplace_back(domain);
+    }
+    ctx.inboxSeq.store(
+        ctx.inboxSeq.load(std::memory_order_relaxed) + 1,
+        std::memory_order_release);
+}
+
+void DnsServer::drainInboxSlow(ServeCtx& ctx) {
+    std::vector<std::string> todo;
+    {
+        std::lock_guard<std::mutex> g(ctx.inboxMu);
+        todo.swap(ctx.inbox);
+        ctx.inboxSeen = ctx.inboxSeq.load(std::memory_order_relaxed);
+    }
+    for (const std::string& d : todo) applyInvalidate(ctx.answers, d);
+}
+
+DnsServer::ServeLock::ServeLock(DnsServer* s, ServeCtx& ctx) {
+    if (!ctx.pooled) return;
+    mu_ = &s->serveMu_;
+    mu_->lock();
+    s->drainInbox(ctx);
+}
+
+DnsServer::ServeLock::~ServeLock() {
+    if (mu_ != nullptr) mu_->unlock();
+}
+
+void DnsServer::countFast(ServeCtx& ctx, bool isSrv, size_t bytes) {
+    HitShards& h = ctx.hits;
+    (isSrv ? h.cntSrv : h.cntA).bump();
+    latHist_->observeShard(isSrv ? h.latSrv : h.latA, 1e-6);  /* sub-us */
+    sizeHist_->observeShard(isSrv ? h.sizeSrv : h.sizeA, (double)bytes);
+}
+
+void DnsServer::foldShards() {
+    static const std::string kA = "type=\"A\"";
+    static const std::string kSrv = "type=\"SRV\"";
+    auto fold = [this](ServeCtx& c) {
+        reqCounter_->fold(kA, c.hits.cntA, c.folds.cntA);
+        reqCounter_->fold(kSrv, c.hits.cntSrv, c.folds.cntSrv);
+        latHist_->fold(kA, c.hits.latA, c.folds.latA);
+        latHist_->fold(kSrv, c.hits.latSrv, c.folds.latSrv);
+        sizeHist_->fold(kA, c.hits.sizeA, c.folds.sizeA);
+        sizeHist_->fold(kSrv, c.hits.sizeSrv, c.folds.sizeSrv);
+    };
+    fold(main_);
+    for (auto& c : pool_) fold(*c);
+    /* the first fast-path reply of either type brings both series */
+    if (queriesServed() != servedSlow_) {
+        reqCounter_->slot(kA);
+        reqCounter_->slot(kSrv);
+        latHist_->seriesRef(kA);
+        latHist_->seriesRef(kSrv);
+        sizeHist_->seriesRef(kA);
+        sizeHist_->seriesRef(kSrv);
+    }
+}
+
 /* Write a memoised answer: copy (or permute) straight into the out
  * buffer, patch id and RD, count it exactly as fastResolve() does. */
-void DnsServer::serveHit(const uint8_t* body, bool isSrv,
+void DnsServer::serveHit(ServeCtx& ctx, const uint8_t* body, bool isSrv,
                          const uint8_t* data, ReplySink& out) {
     const size_t total = answerbody::total(body);
     uint8_t* w = out.openWrite(total);
@@ -462,13 +629,13 @@ void DnsServer::serveHit(const uint8_t* body, bool isSrv,
         memcpy(w, answerbody::wireReply(body), total);
     } else {
         /* Fisher-Yates member order (server.js:40-53, 361): the same
-         * draws from rng_, in the same order, as fastResolve() */
+         * draws from ctx.rng, in the same order, as fastResolve() */
         size_t n = answerbody::serviceMembers(body);
         uint8_t order[answerbody::kMaxMembers];
         for (size_t i = 0; i < n; ++i) order[i] = (uint8_t)i;
         for (size_t i = n; i > 1;) {
             --i;
-            size_t j = rng_() % (i + 1);
+            size_t j = ctx.rng() % (i + 1);
             std::swap(order[i], order[j]);
         }
         answerbody::serviceAssemble(body, order, w);
@@ -477,17 +644,12 @@ void DnsServer::serveHit(const uint8_t* body, bool isSrv,
     w[1] = data[1];
     w[2] = (uint8_t)(w[2] | (data[2] & 0x01));
 
-    ++served_;
-    if (fpCntSrv_ == nullptr) initFastMetricSlots();
-    ++*(isSrv ? fpCntSrv_ : fpCntA_);
-    latHist_->observeFast(*(isSrv ? fpLatSrv_ : fpLatA_), 1e-6);
-    sizeHist_->observeFast(*(isSrv ? fpSizeSrv_ : fpSizeA_),
-                           (double)total);
+    countFast(ctx, isSrv, total);
     BAMD_PROBE2("op-req-done", total, 0);
 }
 
-bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
-                         const ClientInfo& ci, ReplySink& out) {
+bool DnsServer::fastPath(ServeCtx& ctx, const uint8_t* data, size_t len,
+                         bool udp, const ClientInfo& ci, ReplySink& out) {
     /* debug/trace want the slow path's extra detail; info-level
      * per-query lines are emitted from cached fragments */
     if (log_.enabled(LogLevel::Debug)) return false;
@@ -496,14 +658,14 @@ bool DnsServer::fastPath(const uint8_t* data, size_t len, bool udp,
     bool memo = answersOn();
     if (memo) {
         q.hash = answerHash(q);
-        const uint8_t* body = answers_.find(q.hash, q.isSrv ? 33 : 1,
-                                            q.name, q.nlen);
+        const uint8_t* body = ctx.answers.find(q.hash, q.isSrv ? 33 : 1,
+                                               q.name, q.nlen);
         if (body != nullptr) {
-            serveHit(body, q.isSrv, data, out);
+            serveHit(ctx, body, q.isSrv, data, out);
             return true;
         }
     }
-    return fastResolve(q, data, udp, ci, out, memo);
+    return fastResolve(ctx, q, data, udp, ci, out, memo);
 }
 
 bool DnsServer::parseFast(const uint8_t* data, size_t len, FastQuery& q) {
@@ -571,9 +733,10 @@ bool DnsServer::parseFast(const uint8_t* data, size_t len, FastQuery& q) {
     return true;
 }
 
-bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
-                            bool udp, const ClientInfo& ci,
-                            ReplySink& out, bool memo) {
+bool DnsServer::fastResolve(ServeCtx& ctx, const FastQuery& q,
+                            const uint8_t* data, bool udp,
+                            const ClientInfo& ci, ReplySink& out,
+                            bool memo) {
     const bool isSrv = q.isSrv;
     const char* name = q.name;
     const size_t nlen = q.nlen;
@@ -648,7 +811,7 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
         for (size_t i = 0; i < n; ++i) shuffleIdx_[i] = (uint32_t)i;
         for (size_t i = n; i > 1;) {
             --i;
-            size_t j = rng_() % (i + 1);
+            size_t j = ctx.rng() % (i + 1);
             std::swap(shuffleIdx_[i], shuffleIdx_[j]);
         }
 
@@ -675,16 +838,9 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
         w[1] = data[1];
         w[2] = (uint8_t)(w[2] | (data[2] & 0x01));
 
-        ++served_;
-        static const std::string kLabelSrv = "type=\"SRV\"";
-        static const std::string kLabelA2 = "type=\"A\"";
-        /* cached metric slots: the string-keyed lookups were 12% of
-         * binderd user CPU at saturation (gprof, profiles/) */
-        if (fpCntSrv_ == nullptr) initFastMetricSlots();
-        ++*(isSrv ? fpCntSrv_ : fpCntA_);
-        latHist_->observeFast(*(isSrv ? fpLatSrv_ : fpLatA_), 1e-6);
-        sizeHist_->observeFast(*(isSrv ? fpSizeSrv_ : fpSizeA_),
-                               (double)total);
+        /* per-context shards, no string-keyed lookup: those were 12%
+         * of binderd user CPU at saturation (gprof, profiles/) */
+        countFast(ctx, isSrv, total);
         if (log_.enabled(LogLevel::Info)) {
             std::string& f = logOpen(isSrv ? "SRV" : "A");
             bool lfirst = true;
@@ -729,7 +885,7 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
                 }
                 segBytes += s1[i].n + s2[i].n;
             }
-            uint8_t* body = answers_.insert(
+            uint8_t* body = ctx.answers.insert(
                 q.hash, (uint8_t)(isSrv ? 33 : 1), name, nlen,
                 answerbody::serviceBodyLen(n, head.size(), segBytes));
             if (body != nullptr)
@@ -767,11 +923,7 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
     w[1] = data[1];
     w[2] = (uint8_t)(w[2] | (data[2] & 0x01));  /* echo RD */
 
-    ++served_;
-    if (fpCntA_ == nullptr) initFastMetricSlots();
-    ++*fpCntA_;
-    latHist_->observeFast(*fpLatA_, 1e-6);  /* sub-us */
-    sizeHist_->observeFast(*fpSizeA_, (double)wlen);
+    countFast(ctx, false, wlen);
     if (log_.enabled(LogLevel::Info)) {
         std::string& f = logOpen("A");
         f += rec.logA;
@@ -781,8 +933,8 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
     }
     BAMD_PROBE2("op-req-done", wlen, 0);
     if (memo && wlen <= 512) {
-        uint8_t* body = answers_.insert(q.hash, 1, name, nlen,
-                                        answerbody::wireBodyLen(wlen));
+        uint8_t* body = ctx.answers.insert(q.hash, 1, name, nlen,
+                                           answerbody::wireBodyLen(wlen));
         if (body != nullptr)
             answerbody::wireFill(body, rec.wireA.data(), wlen);
     }
@@ -792,17 +944,6 @@ bool DnsServer::fastResolve(const FastQuery& q, const uint8_t* data,
 /* REPLY frame assembled in one header append + one payload append
  * (the string-builder form did ~6 appends + a double copy per reply
  * — gprof showed _M_append at 7.5% of binderd user CPU). */
-void DnsServer::initFastMetricSlots() {
-    static const std::string kA = "type=\"A\"";
-    static const std::string kSrv = "type=\"SRV\"";
-    fpCntA_ = &reqCounter_->slot(kA);
-    fpCntSrv_ = &reqCounter_->slot(kSrv);
-    fpLatA_ = &latHist_->seriesRef(kA);
-    fpLatSrv_ = &latHist_->seriesRef(kSrv);
-    fpSizeA_ = &sizeHist_->seriesRef(kA);
-    fpSizeSrv_ = &sizeHist_->seriesRef(kSrv);
-}
-
 static void appendReplyFrame(std::string& out, uint32_t reqId,
                              const uint8_t* dns, size_t dnsLen) {
     uint32_t plen = (uint32_t)(4 + dnsLen);
@@ -846,20 +987,35 @@ std::function<void(std::vector<uint8_t>)> DnsServer::makeAsyncReply(
     case ReplyTarget::Kind::Bal:
         break;
     }
+    /* Only the connection's owning thread touches its buffers. The
+     * reply is written here when that is the thread we are on (no
+     * pool, or recursion answered synchronously); otherwise it is
+     * posted to the owner's loop. The shared_ptr keeps the connection
+     * object alive either way and `closed` is checked over there. */
     std::shared_ptr<BalConn> self = t.bal->shared_from_this();
     uint32_t reqId = t.reqId;
     return [this, self, reqId](std::vector<uint8_t> wire) {
-        if (self->closed) return;
-        appendReplyFrame(self->out, reqId, wire.data(), wire.size());
-        balFlush(self.get());
+        ServeCtx* ctx = self->ctx;
+        auto deliver = [this, self, ctx, reqId](
+                           const std::vector<uint8_t>& w) {
+            if (self->closed) return;
+            appendReplyFrame(self->out, reqId, w.data(), w.size());
+            balFlush(*ctx, self.get());
+        };
+        if (ctx->loop->inLoopThread()) {
+            deliver(wire);
+            return;
+        }
+        ctx->loop->postFromThread(
+            [deliver, wire = std::move(wire)]() { deliver(wire); });
     };
 }
 
-bool DnsServer::process(const uint8_t* data, size_t len, bool udp,
-                        const ClientInfo& ci, ReplySink& out,
+bool DnsServer::process(ServeCtx& ctx, const uint8_t* data, size_t len,
+                        bool udp, const ClientInfo& ci, ReplySink& out,
                         const ReplyTarget& target) {
     BAMD_PROBE2("op-req-start", len, (int)udp);
-    if (fastPath(data, len, udp, ci, out)) return true;
+    if (fastPath(ctx, data, len, udp, ci, out)) return true;
     return slowPath(data, len, udp, ci, out, target);
 }
 
@@ -938,7 +1094,7 @@ void DnsServer::afterQuery(const Message& query, const Message& resp,
                            const QueryResult& qr, const ClientInfo& ci,
                            size_t bytesSent, int64_t startUs,
                            const QueryTimers& tm) {
-    ++served_;
+    ++servedSlow_;
     int64_t latUs = nowUs() - startUs;
     int64_t lat = latUs / 1000;
     BAMD_PROBE2("op-req-done", bytesSent, (int)resp.header.rcode);
@@ -1056,7 +1212,7 @@ void DnsServer::onUdpReadable() {
             target.src = &rxAddrs_[i];  /* copied if it goes async */
             target.srcLen = srcLen;
             bool sync = process(
-                rxArena_.data() + (size_t)i * kInBuf, rxHdrs_[i].msg_len,
+                main_, rxArena_.data() + (size_t)i * kInBuf, rxHdrs_[i].msg_len,
                 true, ci, sink, target);
             if (sync && !out.empty()) {
                 txAddrs_[nOut] = rxAddrs_[i];
@@ -1174,7 +1330,7 @@ void DnsServer::onTcpConn(TcpConn* c, uint32_t events) {
         ReplyTarget target{ReplyTarget::Kind::Tcp};
         target.tcp = c;
         bool sync = process(
-            (const uint8_t*)c->in.data() + 2, mlen, false, c->ci, sink,
+            main_, (const uint8_t*)c->in.data() + 2, mlen, false, c->ci, sink,
             target);
         if (sync) {
             if (!out.empty()) {
@@ -1198,24 +1354,39 @@ void DnsServer::onBalAccept() {
         int sz = 4 << 20;
         setsockopt(fd, SOL_SOCKET, SO_SNDBUF, &sz, sizeof(sz));
         setsockopt(fd, SOL_SOCKET, SO_RCVBUF, &sz, sizeof(sz));
-        auto conn = std::make_shared<BalConn>();
-        conn->fd = fd;
-        BalConn* raw = conn.get();
-        balConns_[fd] = std::move(conn);
-        loop_->addFd(fd, EPOLLIN,
-                     [this, raw](uint32_t ev) { onBalConn(raw, ev); });
+        if (pool_.empty()) {
+            adoptBal(main_, fd);
+            continue;
+        }
+        /* round-robin over the pool; the connection object is made by
+         * the thread that will own it */
+        ServeCtx* ctx = pool_[nextPool_++ % pool_.size()].get();
+        ctx->loop->postFromThread([this, ctx, fd]() { adoptBal(*ctx, fd); });
     }
 }
 
-void DnsServer::closeBal(BalConn* c) {
-    if (c->closed) return;
-    c->closed = true;
-    loop_->delFd(c->fd);
-    close(c->fd);
-    balConns_.erase(c->fd);
+/* on ctx's thread */
+void DnsServer::adoptBal(ServeCtx& ctx, int fd) {
+    auto conn = std::make_shared<BalConn>();
+    conn->ctx = &ctx;
+    conn->fd = fd;
+    BalConn* raw = conn.get();
+    ctx.balConns[fd] = std::move(conn);
+    ServeCtx* cp = &ctx;
+    ctx.loop->addFd(fd, EPOLLIN, [this, cp, raw](uint32_t ev) {
+        onBalConn(*cp, raw, ev);
+    });
 }
 
-void DnsServer::balFlush(BalConn* c) {
+void DnsServer::closeBal(ServeCtx& ctx, BalConn* c) {
+    if (c->closed) return;
+    c->closed = true;
+    ctx.loop->delFd(c->fd);
+    close(c->fd);
+    ctx.balConns.erase(c->fd);
+}
+
+void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
     while (c->outOff < c->out.size()) {
         ssize_t nw = write(c->fd, c->out.data() + c->outOff,
                            c->out.size() - c->outOff);
@@ -1233,28 +1404,32 @@ void DnsServer::balFlush(BalConn* c) {
             }
             if (!c->writeBlocked) {
                 c->writeBlocked = true;
-                loop_->modFd(c->fd, EPOLLIN | EPOLLOUT);
+                ctx.loop->modFd(c->fd, EPOLLIN | EPOLLOUT);
             }
             return;
         }
-        closeBal(c);
+        closeBal(ctx, c);
         return;
     }
     c->out.clear();
     c->outOff = 0;
     if (c->writeBlocked) {
         c->writeBlocked = false;
-        loop_->modFd(c->fd, EPOLLIN);
+        ctx.loop->modFd(c->fd, EPOLLIN);
     }
 }
 
-void DnsServer::onBalConn(BalConn* c, uint32_t events) {
-    std::shared_ptr<BalConn> keep = balConns_[c->fd];
+/* Runs on ctx's thread. For a pool thread that means without the
+ * serving lock: table hits, PINGs and the socket I/O touch nothing but
+ * ctx and c. Everything else takes the lock (ServeLock) for the one
+ * frame it is about, at that frame's place in the batch. */
+void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
+    std::shared_ptr<BalConn> keep = ctx.balConns[c->fd];
     if (events & (EPOLLHUP | EPOLLERR)) {
-        closeBal(c);
+        closeBal(ctx, c);
         return;
     }
-    if (events & EPOLLOUT) balFlush(c);
+    if (events & EPOLLOUT) balFlush(ctx, c);
     if (c->closed || !(events & EPOLLIN)) return;
 
     /* Bounded batch per epoll event: the GSO-era balancer can queue
@@ -1281,9 +1456,13 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
             continue;
         }
         if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
-        closeBal(c);
+        closeBal(ctx, c);
         return;
     }
+    /* invalidations posted before these bytes were read apply before
+     * any of them is answered */
+    drainInbox(ctx);
+    AnswerTable& answers = ctx.answers;
 
     /* Frames are parsed by advancing the buffer's cursor; the partial
      * frame left at the end moves to the front once, below. */
@@ -1332,7 +1511,7 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
                 if (memo && parseFast(p.qf.dns, p.qf.dnsLen, p.q)) {
                     p.kind = kFastQuery;
                     p.q.hash = answerHash(p.q);
-                    answers_.prefetchSlot(p.q.hash);
+                    answers.prefetchSlot(p.q.hash);
                 }
             } else {
                 p.kind = kSkip;
@@ -1344,10 +1523,10 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
             PipeFrame& p = ring[probed++ & (kPipeDepth - 1)];
             if (p.kind != kFastQuery) continue;
             uint32_t blen = 0;
-            p.off = answers_.probe(p.q.hash, &blen);
-            p.gen = answers_.generation();
+            p.off = answers.probe(p.q.hash, &blen);
+            p.gen = answers.generation();
             if (p.off != AnswerTable::kNone)
-                answers_.prefetchBlob(p.off, blen);
+                answers.prefetchBlob(p.off, blen);
         }
         /* stage 3: serve the oldest frame */
         PipeFrame& p = ring[served++ & (kPipeDepth - 1)];
@@ -1363,13 +1542,13 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
             const uint8_t qt = p.q.isSrv ? 33 : 1;
             const uint8_t* body = nullptr;
             if (p.off != AnswerTable::kNone &&
-                p.gen == answers_.generation())
-                body = answers_.at(p.off, qt, p.q.name, p.q.nlen);
+                p.gen == answers.generation())
+                body = answers.at(p.off, qt, p.q.name, p.q.nlen);
             if (body == nullptr)  /* not probed, stale, or a collision */
-                body = answers_.find(p.q.hash, qt, p.q.name, p.q.nlen);
+                body = answers.find(p.q.hash, qt, p.q.name, p.q.nlen);
             if (body != nullptr) {
                 BAMD_PROBE2("op-req-start", qf.dnsLen, (int)udp);
-                serveHit(body, p.q.isSrv, qf.dns, sink);
+                serveHit(ctx, body, p.q.isSrv, qf.dns, sink);
                 continue;
             }
         }
@@ -1381,23 +1560,27 @@ void DnsServer::onBalConn(BalConn* c, uint32_t events) {
         ReplyTarget target{ReplyTarget::Kind::Bal};
         target.bal = c;
         target.reqId = qf.reqId;
+        /* not a hit: the shared code, under the serving lock when this
+         * is a pool thread (which drains its inbox first, so what it
+         * memoises is no older than what it has been told to drop) */
+        ServeLock lock(this, ctx);
         if (p.kind == kFastQuery) {
             /* table miss: the fast path proper, from the parse at hand */
             BAMD_PROBE2("op-req-start", qf.dnsLen, (int)udp);
-            if (!fastResolve(p.q, qf.dns, udp, ci, sink, true))
+            if (!fastResolve(ctx, p.q, qf.dns, udp, ci, sink, true))
                 slowPath(qf.dns, qf.dnsLen, udp, ci, sink, target);
         } else {
-            process(qf.dns, qf.dnsLen, udp, ci, sink, target);
+            process(ctx, qf.dns, qf.dnsLen, udp, ci, sink, target);
         }
     }
     if (st == bsock::FrameStatus::Bad) {
-        closeBal(c);
+        closeBal(ctx, c);
         return;
     }
     /* a synchronous recursion reply may have hit a write error */
     if (c->closed) return;
     c->in.compact();
-    balFlush(c);
+    balFlush(ctx, c);
 }
 
 }  // namespace bamd

@@ -10,7 +10,10 @@
  *  - responses are encoded straight into a flat TX arena;
  *  - the balancer hop is a framed protocol over a UNIX stream socket
  *    ("bsock1", see balancer/protocol.hpp) carrying the original client
- *    address, like mname's listenBalancer (server.js:621-631).
+ *    address, like mname's listenBalancer (server.js:621-631);
+ *  - balancer connections can be served by a pool of threads, each with
+ *    an event loop and an answer table of its own (ServeCtx below;
+ *    ownership and locking rules in docs/ARCHITECTURE.md).
  */
 #pragma once
 
@@ -18,11 +21,14 @@
 #include <sys/socket.h>
 #include <sys/un.h>
 
+#include <atomic>
 #include <functional>
 #include <random>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../common/log.hpp"
@@ -39,7 +45,15 @@ struct ServerOptions {
     std::string host;  // bind address; empty = all interfaces
     uint16_t port = 53;
     std::string balancerSocket;  // unix socket path; empty = none
+    /* threads serving balancer connections; 1 = none besides the main
+     * thread. See defaultServeThreads(). */
+    int serveThreads = 1;
 };
+
+/* clamp(cpus / 4, 1, 4), cpus being what this process may actually use:
+ * the cgroup CPU quota (v2 cpu.max, then v1 cfs), else the affinity
+ * mask - never the machine's hardware thread count. */
+int defaultServeThreads();
 
 struct QueryTimers {
     int64_t parseUs = 0;
@@ -126,9 +140,13 @@ class DnsServer {
 
     uint16_t boundPort() const { return boundPort_; }
 
-    uint64_t queriesServed() const { return served_; }
+    uint64_t queriesServed() const;
 
   private:
+    /* whether start() runs a pool: serveThreads >= 2, a balancer
+     * socket, and the answer table in use (fixed at start) */
+    bool pooled() const;
+
     struct TcpConn : std::enable_shared_from_this<TcpConn> {
         int fd;
         std::string in;
@@ -139,7 +157,9 @@ class DnsServer {
         bool closed = false;
         int64_t lastActivityMs = 0;
     };
+    struct ServeCtx;
     struct BalConn : std::enable_shared_from_this<BalConn> {
+        ServeCtx* ctx = nullptr;  /* owner; only its thread touches us */
         int fd;
         FrameBuf in;
         std::string out;
@@ -171,7 +191,8 @@ class DnsServer {
     void onTcpAccept();
     void onTcpConn(TcpConn* c, uint32_t events);
     void onBalAccept();
-    void onBalConn(BalConn* c, uint32_t events);
+    void adoptBal(ServeCtx& ctx, int fd);
+    void onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events);
 
     /*
      * Decode + resolve + encode. Returns true when the answer is
@@ -179,10 +200,10 @@ class DnsServer {
      * the packet is dropped. Returns false when handed to recursion;
      * delivery then goes through a closure built from `target`.
      */
-    bool process(const uint8_t* data, size_t len, bool udp,
+    bool process(ServeCtx& ctx, const uint8_t* data, size_t len, bool udp,
                  const ClientInfo& ci, ReplySink& out,
                  const ReplyTarget& target);
-    bool fastPath(const uint8_t* data, size_t len, bool udp,
+    bool fastPath(ServeCtx& ctx, const uint8_t* data, size_t len, bool udp,
                   const ClientInfo& ci, ReplySink& out);
     /* The rest of process() once fastPath() has declined. */
     bool slowPath(const uint8_t* data, size_t len, bool udp,
@@ -212,25 +233,101 @@ class DnsServer {
     static bool parseFast(const uint8_t* data, size_t len, FastQuery& q);
     /* policy checks + store lookup + cached-record serve (the fast
      * path proper); memoises what it served when `memo` is set */
-    bool fastResolve(const FastQuery& q, const uint8_t* data, bool udp,
-                     const ClientInfo& ci, ReplySink& out, bool memo);
+    bool fastResolve(ServeCtx& ctx, const FastQuery& q,
+                     const uint8_t* data, bool udp, const ClientInfo& ci,
+                     ReplySink& out, bool memo);
     /* serve a memoised answer body (answerbody:: layouts) */
-    void serveHit(const uint8_t* body, bool isSrv, const uint8_t* data,
-                  ReplySink& out);
+    void serveHit(ServeCtx& ctx, const uint8_t* body, bool isSrv,
+                  const uint8_t* data, ReplySink& out);
     /* info and debug levels bypass the answer table: their per-query
      * log lines are built from the records, not from the memo */
     bool answersOn() const { return !log_.enabled(LogLevel::Info); }
     void onStoreInvalidate(std::string_view domain);
+    static void applyInvalidate(AnswerTable& t, std::string_view domain);
+
+    /* the hit path's metric shards (metrics.hpp), per context */
+    struct HitShards {
+        CounterShard cntA, cntSrv;
+        Histogram::Shard latA, latSrv, sizeA, sizeSrv;
+    };
+    struct HitFolds {
+        CounterFold cntA, cntSrv;
+        Histogram::Fold latA, latSrv, sizeA, sizeSrv;
+    };
+    void countFast(ServeCtx& ctx, bool isSrv, size_t bytes);
+    void foldShards();  /* under the serving lock, before a scrape */
 
     /*
-     * Answer table: memo of fastResolve()'s replies, (qname, qtype) ->
-     * finished bytes. Inserted only by fastResolve(); dropped per name
-     * through the store's invalidate hook, wholesale when the store's
-     * readiness changes. An SRV entry is hashed on the service's
-     * domain (the A entry on the whole name) so both can be found from
-     * the domain alone.
+     * Serving context: all that the hit path touches, owned by one
+     * thread. The main thread has one (UDP, TCP, and the balancer
+     * connections when no pool runs); each pool thread has one.
+     *
+     * answers - the answer table: memo of fastResolve()'s replies,
+     * (qname, qtype) -> finished bytes. Inserted only by fastResolve()
+     * run by the owning thread; dropped per name through the store's
+     * invalidate hook, wholesale when the store's readiness changes.
+     * An SRV entry is hashed on the service's domain (the A entry on
+     * the whole name) so both can be found from the domain alone.
+     *
+     * inbox - invalidations for a pool thread's table, appended by
+     * the store hook (main thread, serving lock held), applied by the
+     * owner in drainInbox(): after every read() and after every take
+     * of the serving lock. An empty string means clear all.
+     *
+     * Aligned so that two threads' contexts never share a cache line.
      */
-    AnswerTable answers_;
+    struct alignas(64) ServeCtx {
+        AnswerTable answers;
+        std::mt19937 rng{std::random_device{}()};
+        HitShards hits;
+        EventLoop* loop = nullptr;
+        std::map<int, std::shared_ptr<BalConn>> balConns;
+        bool pooled = false;
+
+        std::atomic<uint64_t> inboxSeq{0};
+        uint64_t inboxSeen = 0;  /* owner only */
+        std::mutex inboxMu;
+        std::vector<std::string> inbox;
+
+        HitFolds folds;  /* scraping side */
+
+        /* pool threads only */
+        std::unique_ptr<EventLoop> ownLoop;
+        std::thread thread;
+    };
+    void postInvalidate(ServeCtx& ctx, std::string_view domain);
+    void drainInbox(ServeCtx& ctx) {
+        if (ctx.inboxSeq.load(std::memory_order_acquire) != ctx.inboxSeen)
+            drainInboxSlow(ctx);
+    }
+    void drainInboxSlow(ServeCtx& ctx);
+    /* a pooled inbox longer than this collapses into one clear-all */
+    static constexpr size_t kInboxMax = 4096;
+
+    /* Takes the serving lock for a pool thread (and drains its inbox
+     * once it has it); nothing for the main context, whose loop holds
+     * the lock already. */
+    class ServeLock {
+      public:
+        ServeLock(DnsServer* s, ServeCtx& ctx);
+        ~ServeLock();
+        ServeLock(const ServeLock&) = delete;
+        ServeLock& operator=(const ServeLock&) = delete;
+
+      private:
+        std::mutex* mu_ = nullptr;
+    };
+
+    ServeCtx main_;
+    std::vector<std::unique_ptr<ServeCtx>> pool_;
+    size_t nextPool_ = 0;  /* round-robin cursor of onBalAccept() */
+    /* The serving lock: guards everything that is not a ServeCtx's
+     * own - store, engine, recursion, logger, the collector's maps,
+     * the scratch buffers below, the main loop's tables. With a pool
+     * the main loop holds it whenever it dispatches. */
+    std::mutex serveMu_;
+    void stopPool();
+
     static uint64_t answerHash(const FastQuery& q) {
         return q.isSrv ? AnswerTable::hashKey(q.name + q.keyOff,
                                               q.nlen - q.keyOff, 33)
@@ -248,15 +345,6 @@ class DnsServer {
     std::vector<uint8_t> encScratch_;  /* slow-path encode, frame mode */
     std::vector<uint8_t> tcpOut_;      /* TCP sync reply scratch */
     std::vector<uint32_t> shuffleIdx_;
-    std::mt19937 rng_{std::random_device{}()};
-    void initFastMetricSlots();
-    /* cached hot-path metric slots (stable map nodes) */
-    uint64_t* fpCntA_ = nullptr;
-    uint64_t* fpCntSrv_ = nullptr;
-    Histogram::Series* fpLatA_ = nullptr;
-    Histogram::Series* fpLatSrv_ = nullptr;
-    Histogram::Series* fpSizeA_ = nullptr;
-    Histogram::Series* fpSizeSrv_ = nullptr;
     std::string logFields_, logScratch_;   /* afterQuery log buffers */
 
   public:
@@ -273,14 +361,15 @@ class DnsServer {
 
     void tcpFlush(TcpConn* c);
     void sweepIdleTcp();
-    void balFlush(BalConn* c);
+    void balFlush(ServeCtx& ctx, BalConn* c);
     void closeTcp(TcpConn* c);
-    void closeBal(BalConn* c);
+    void closeBal(ServeCtx& ctx, BalConn* c);
 
     EventLoop* loop_;
     Logger log_;
     ServerOptions opts_;
     Engine* engine_;
+    Collector* collector_;
     RecursionIface* recursion_ = nullptr;
 
     Counter* reqCounter_ = nullptr;
@@ -291,13 +380,12 @@ class DnsServer {
     int tcpFd_ = -1;
     int balFd_ = -1;
     uint16_t boundPort_ = 0;
-    uint64_t served_ = 0;
+    uint64_t servedSlow_ = 0;  /* afterQuery()'s, under the serving lock */
 
     /* shared_ptr: async recursion replies may outlive the connection
      * (fds get reused; a closed conn object must stay valid until the
      * last in-flight reply fires and observes `closed`). */
     std::map<int, std::shared_ptr<TcpConn>> tcpConns_;
-    std::map<int, std::shared_ptr<BalConn>> balConns_;
 
     /* UDP batched I/O arenas. */
     static constexpr int kBatch = 64;

@@ -6,6 +6,11 @@ consumed per component — the denominator that bounds qps on the
 quota-capped bench boxes (profiles/SCALING.md round 2).
 
 usage: cpu_apportion.py [--procs 8] [--workers 8] [--threads 6]
+                        [--window 256] [--ramp 2]
+
+The generator is given far more queries than any window can use: a
+budget that runs out inside the window (100 M did, once the chain
+passed 12.5 M qps) reads as a *lower* rate the faster the chain is.
 """
 import argparse
 import json
@@ -39,6 +44,10 @@ def main():
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--threads", type=int, default=6)
     ap.add_argument("--seconds", type=float, default=6.0)
+    ap.add_argument("--window", type=int, default=256,
+                    help="dnsblast in-flight queries per socket")
+    ap.add_argument("--ramp", type=float, default=2.0,
+                    help="seconds of load before the sampling window")
     ap.add_argument("--no-gso", action="store_true")
     args = ap.parse_args()
 
@@ -57,7 +66,7 @@ def main():
     bench.wait_balancer_ready(port, args.procs, tmp)
 
     cmd = [str(REPO / "bin" / "dnsblast"), "-s", "127.0.0.1",
-           "-p", str(port), "-n", "100000000", "-c", "256",
+           "-p", str(port), "-n", "4000000000", "-c", str(args.window),
            "-t", str(args.threads), "-P", "8", "-f", str(names_file),
            "-B", "127.0.1.1", "-T", "10000"]
     if args.no_gso:
@@ -70,7 +79,7 @@ def main():
             s.connect(str(tmp / "stats.sock"))
             return json.loads(s.recv(1 << 20).decode())
     try:
-        time.sleep(2.0)  # ramp
+        time.sleep(args.ramp)
         pids = {"dnsblast": [blast.pid], "balancer": [bal.pid],
                 "zkd": [zkd.proc.pid],
                 "binderd": [b.proc.pid for b in backends]}
@@ -83,7 +92,7 @@ def main():
         st1 = balstat()
         out = {"window_s": round(dt, 2), "procs": args.procs,
                "workers": args.workers, "threads": args.threads,
-               "gso": not args.no_gso,
+               "window": args.window, "ramp_s": args.ramp, "gso": not args.no_gso,
                "qps": round((st1["udp_replies"] -
                              st0["udp_replies"]) / dt)}
         total = 0.0
