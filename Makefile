@@ -127,6 +127,19 @@ $(BUILD)/answertab_check: native/server/answertab_check_main.cpp \
 check-answertab: $(BUILD)/answertab_check
 	$(BUILD)/answertab_check 1 100000
 
+# Sanitizer run of the balancer's reply-run grouping (replyruns.hpp) in a
+# stand-alone program with a recording sink: fixed and seeded random
+# reply sequences, sinks that fail runs. Host-only, CPU-only.
+$(BUILD)/replyruns_check: native/balancer/replyruns_check_main.cpp \
+		native/balancer/replyruns.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-replyruns: $(BUILD)/replyruns_check
+	$(BUILD)/replyruns_check 1 300
+
 # ThreadSanitizer run of the serving-thread pool: binderd itself (a daemon
 # with its own main) built with -fsanitize=thread into $(BUILD)/tsan, and
 # the pool's tests plus the two suites that pin reply order and ingress
@@ -175,4 +188,4 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
-	check-serve-threads release
+	check-replyruns check-serve-threads release

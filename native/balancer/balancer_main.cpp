@@ -49,7 +49,9 @@
 #include "../common/json.hpp"
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
+#include "../server/framebuf.hpp"
 #include "protocol.hpp"
+#include "replyruns.hpp"
 
 using namespace bamd;
 
@@ -179,12 +181,21 @@ static_assert(sizeof(PendingSlot) <= 32, "keep the ring compact");
  * tiny values let tests exercise the overwrite accounting). */
 size_t g_pendingSlots = 32768;
 
+/* bounded batch per backend event (level-triggered epoll re-fires):
+ * draining a many-MB reply backlog in one go stalls the worker's other
+ * duties for milliseconds */
+constexpr size_t kMaxReadPerEvent = 256 * 1024;
+constexpr size_t kReadChunk = 65536;
+
 struct Backend {
     int id;
     std::string path;
     int fd = -1;
     bool ok = false;
-    std::string in, out;
+    /* rests at one event's reads (the loop stops at the first read
+     * that ends past the quota) plus a partial frame */
+    FrameBuf in{kMaxReadPerEvent + 2 * kReadChunk};
+    std::string out;
     bool writeBlocked = false;
     uint32_t nextReq = 1;
     std::unique_ptr<PendingSlot[]> pending;  /* lazily sized ring */
@@ -253,9 +264,10 @@ class Balancer {
     Backend* pickBackendFast(const struct sockaddr_storage& ss);
     Backend* chooseLeastLoaded();
     void onUdpReadable();
+    Backend* routeFor(const struct sockaddr_storage& src);
     void handleUdpQuery(const uint8_t* dns, size_t dnsLen,
                         const struct sockaddr_storage& src,
-                        int64_t expiry, std::set<Backend*>& touched);
+                        int64_t expiry, Backend* be);
     void onTcpAccept();
     void onTcpClient(std::shared_ptr<TcpClient> c, uint32_t ev);
     void tcpClientFlush(TcpClient* c);
@@ -285,8 +297,12 @@ class Balancer {
     std::map<int, std::shared_ptr<TcpClient>> tcpClients_;
     int nextBackendId_ = 1;
     int salvageDepth_ = 0;  /* bounds backendDown->salvage recursion */
-    bool replyGso_ = true;  /* UDP_SEGMENT reply runs (auto-fallback) */
     uint64_t udpQueries_ = 0, udpReplies_ = 0, drops_ = 0;
+    /* hot-path shape counters (stats socket), beside the run counters
+     * replyRuns_ keeps: backend read() calls that returned data, UDP
+     * messages received (a GRO message counts once however many
+     * queries it carries) */
+    uint64_t backendReads_ = 0, udpRxMsgs_ = 0;
 
     static constexpr size_t kMaxRemotes = 262144;
     static constexpr size_t kMaxPending = 16384;
@@ -307,9 +323,86 @@ class Balancer {
     struct iovec rxIovs_[kBatch];
     struct sockaddr_storage rxAddrs_[kBatch];
     char rxCtrl_[kBatch][CMSG_SPACE(sizeof(uint16_t))];
-    struct mmsghdr replyHdrs_[kBatch];
-    struct iovec replyIovs_[kBatch];
-    struct sockaddr_storage replyAddrs_[kBatch];
+
+    /* Route of the previous datagram's source address. All segments of
+     * a GRO message share one source and a worker sees few client
+     * addresses, so most messages skip the affinity maps. Holds a bare
+     * pointer: dropRouteCache() whenever a backend goes down (removal
+     * goes through backendDown) or the affinity table is reset. */
+    struct {
+        Backend* be = nullptr;
+        uint8_t family = 0;
+        uint8_t addr[16];
+    } routeCache_;
+    void dropRouteCache() { routeCache_.be = nullptr; }
+
+    /* backends that were handed queries and still need a flush */
+    struct Touched {
+        static constexpr int kMax = 16;
+        Backend* v[kMax];
+        int n = 0;
+        bool add(Backend* b) {
+            for (int i = n - 1; i >= 0; --i)
+                if (v[i] == b) return true;
+            if (n == kMax) return false;
+            v[n++] = b;
+            return true;
+        }
+    };
+    void touch(Touched& t, Backend* be, Backend* skip = nullptr) {
+        if (t.add(be)) return;
+        flushTouched(t, skip);
+        t.add(be);
+    }
+    void flushTouched(Touched& t, Backend* skip = nullptr) {
+        int n = t.n;
+        t.n = 0;
+        for (int i = 0; i < n; ++i)
+            if (t.v[i] != skip) backendFlush(t.v[i]);
+    }
+
+    /* UDP replies leave as UDP_SEGMENT runs or through a sendmmsg
+     * batch; replyruns.hpp decides which, this does the sending */
+    struct UdpSink {
+        const int* fd;
+        int sendRun(const struct sockaddr* dst, socklen_t dlen,
+                    struct iovec* iov, size_t n, uint16_t seg) {
+            struct msghdr mh {};
+            mh.msg_name = const_cast<struct sockaddr*>(dst);
+            mh.msg_namelen = dlen;
+            mh.msg_iov = iov;
+            mh.msg_iovlen = n;
+            char cbuf[CMSG_SPACE(sizeof(uint16_t))] = {0};
+            mh.msg_control = cbuf;
+            mh.msg_controllen = sizeof(cbuf);
+            struct cmsghdr* cm = CMSG_FIRSTHDR(&mh);
+            cm->cmsg_level = SOL_UDP;
+            cm->cmsg_type = UDP_SEGMENT;
+            cm->cmsg_len = CMSG_LEN(sizeof(uint16_t));
+            memcpy(CMSG_DATA(cm), &seg, sizeof(seg));
+            return sendmsg(*fd, &mh, 0) < 0 ? errno : 0;
+        }
+        void sendOne(const struct sockaddr* dst, socklen_t dlen,
+                     struct iovec* iov) {
+            struct msghdr m1 {};
+            m1.msg_name = const_cast<struct sockaddr*>(dst);
+            m1.msg_namelen = dlen;
+            m1.msg_iov = iov;
+            m1.msg_iovlen = 1;
+            ssize_t r1 = sendmsg(*fd, &m1, 0);
+            (void)r1;
+        }
+        void sendBatch(struct mmsghdr* hdrs, unsigned n) {
+            unsigned sent = 0;
+            while (sent < n) {
+                int rv = sendmmsg(*fd, hdrs + sent, n - sent, 0);
+                if (rv <= 0) break;
+                sent += (unsigned)rv;
+            }
+        }
+    };
+    UdpSink udpSink_{&udpFd_};
+    ReplyRuns<UdpSink> replyRuns_{udpSink_};
 };
 
 bool Balancer::start() {
@@ -358,6 +451,18 @@ bool Balancer::start() {
     if (!doBind(udpFd_) || !doBind(tcpFd_) || listen(tcpFd_, 512) != 0) {
         log_.error({{"port", Json((int)port_)}}, "balancer bind failed");
         return false;
+    }
+    /* recvmmsg arrays are laid out once; onUdpReadable() resets only
+     * what the kernel overwrites */
+    memset(rxHdrs_, 0, sizeof(rxHdrs_));
+    for (int i = 0; i < kBatch; ++i) {
+        rxIovs_[i] = {rxArena_.data() + (size_t)i * kRxBufSz, kRxBufSz};
+        rxHdrs_[i].msg_hdr.msg_iov = &rxIovs_[i];
+        rxHdrs_[i].msg_hdr.msg_iovlen = 1;
+        rxHdrs_[i].msg_hdr.msg_name = &rxAddrs_[i];
+        rxHdrs_[i].msg_hdr.msg_namelen = sizeof(rxAddrs_[i]);
+        rxHdrs_[i].msg_hdr.msg_control = rxCtrl_[i];
+        rxHdrs_[i].msg_hdr.msg_controllen = sizeof(rxCtrl_[i]);
     }
     loop_->addFd(udpFd_, EPOLLIN, [this](uint32_t) { onUdpReadable(); });
     loop_->addFd(tcpFd_, EPOLLIN, [this](uint32_t) { onTcpAccept(); });
@@ -474,6 +579,7 @@ void Balancer::backendDown(Backend* be) {
         be->fd = -1;
     }
     be->ok = false;
+    dropRouteCache();
     be->in.clear();
     /* Salvage: frames we queued but never flushed into the dead
      * connection can be re-dispatched to a healthy backend instead of
@@ -503,7 +609,7 @@ void Balancer::backendDown(Backend* be) {
 
     if (!unsent.empty() && salvageDepth_ < 4) {
         salvageDepth_++;
-        std::set<Backend*> touched;
+        Touched touched;
         int64_t expiry = monotonicMillis() + kReplyTtlMs;
         size_t off = 0;
         while (unsent.size() - off >= bsock::kHeaderLen) {
@@ -534,14 +640,15 @@ void Balancer::backendDown(Backend* be) {
                     sa->sin6_port = htons(port);
                     memcpy(&sa->sin6_addr, payload + 8, 16);
                 }
+                Backend* to = routeFor(src);
                 handleUdpQuery(payload + bsock::kQueryHeadLen,
                                plen - bsock::kQueryHeadLen, src,
-                               expiry, touched);
+                               expiry, to);
+                if (to != nullptr) touch(touched, to, be);
             }
             off += bsock::kHeaderLen + plen;
         }
-        for (Backend* tb : touched)
-            if (tb != be) backendFlush(tb);
+        flushTouched(touched, be);
         salvageDepth_--;
     }
 }
@@ -589,19 +696,19 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
         return;
     }
     if (ev & EPOLLOUT) backendFlush(be.get());
-    if (!(ev & EPOLLIN)) return;
+    if (!(ev & EPOLLIN) || be->fd < 0) return;
 
-    /* bounded batch per event (level-triggered epoll re-fires):
-     * draining a many-MB reply backlog in one go stalls the worker's
-     * other duties for milliseconds */
-    constexpr size_t kMaxReadPerEvent = 256 * 1024;
+    /* straight into the frame buffer's tail; a read that returns
+     * less than was asked for has drained the socket, so the EAGAIN
+     * read that used to end every event is not made */
     size_t got = 0;
-    char buf[65536];
-    while (be->fd >= 0 && got < kMaxReadPerEvent) {
-        ssize_t nr = read(be->fd, buf, sizeof(buf));
+    while (got < kMaxReadPerEvent) {
+        ssize_t nr = read(be->fd, be->in.tail(kReadChunk), kReadChunk);
         if (nr > 0) {
-            be->in.append(buf, (size_t)nr);
+            be->in.commit((size_t)nr);
             got += (size_t)nr;
+            backendReads_++;
+            if ((size_t)nr < kReadChunk) break;
             continue;
         }
         if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
@@ -610,148 +717,34 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
         return;
     }
 
-    /* Walk complete frames without per-frame erase; UDP replies are
-     * batched (a syscall per reply was the balancer's top cost at
-     * high QPS), and — because worker->backend affinity slices give
-     * each worker few flows — consecutive same-destination equal-size
-     * replies form runs that go out as ONE UDP_SEGMENT super-packet
-     * (multi-iov, no copy): the reply hop's kernel cost is per RUN,
-     * not per packet. Falls back to sendmmsg when GSO is refused. */
-    constexpr int kReplyBatch = kBatch;
-    struct mmsghdr* rh = replyHdrs_;
-    struct iovec* riov = replyIovs_;
-    struct sockaddr_storage* raddr = replyAddrs_;
-    int nReply = 0;
-    int order[kReplyBatch];
-    auto sameDest = [&](int a, int b) {
-        if (raddr[a].ss_family != raddr[b].ss_family) return false;
-        if (raddr[a].ss_family == AF_INET) {
-            auto* x = (const struct sockaddr_in*)&raddr[a];
-            auto* y = (const struct sockaddr_in*)&raddr[b];
-            return x->sin_port == y->sin_port &&
-                   x->sin_addr.s_addr == y->sin_addr.s_addr;
+    /* Walk the complete frames. UDP replies are filed into reply runs
+     * as they are parsed (replyruns.hpp): same-destination equal-size
+     * replies of the WHOLE event leave as UDP_SEGMENT super-packets,
+     * the rest through one sendmmsg batch, and all of them before this
+     * handler returns.
+     *
+     * Invariant: the iovecs held by replyRuns_ point into be->in. All
+     * reads of the event are done (above), and nothing may move or
+     * reuse that buffer - no tail(), compact(), clear(), so no
+     * backendDown() either - until replyRuns_.finish() has run. */
+    bool bad = false;
+    for (;;) {
+        bsock::FrameView f;
+        bsock::FrameStatus st = bsock::nextFrame(be->in, f);
+        if (st == bsock::FrameStatus::NeedMore) break;
+        if (st == bsock::FrameStatus::Bad) {
+            bad = true;
+            break;
         }
-        auto* x = (const struct sockaddr_in6*)&raddr[a];
-        auto* y = (const struct sockaddr_in6*)&raddr[b];
-        return x->sin6_port == y->sin6_port &&
-               memcmp(&x->sin6_addr, &y->sin6_addr, 16) == 0;
-    };
-    auto flushReplies = [&]() {
-        if (nReply == 0) return;
-        for (int i = 0; i < nReply; ++i) order[i] = i;
-        std::sort(order, order + nReply, [&](int a, int b) {
-            int c = memcmp(&raddr[a], &raddr[b], sizeof(raddr[a]));
-            if (c != 0) return c < 0;
-            return riov[a].iov_len > riov[b].iov_len;
-        });
-        int i = 0;
-        int nSingle = 0;
-        static thread_local std::vector<struct iovec> runIovs;
-        while (i < nReply) {
-            /* run: same destination, equal sizes (a shorter one may
-             * close the run — UDP_SEGMENT's trailing segment) */
-            int j = i + 1;
-            size_t seg = riov[order[i]].iov_len;
-            /* one UDP datagram caps at ~64KB: bound the run so large
-             * replies can never push the super-packet past it */
-            size_t maxRun = seg > 0 ? 60000 / seg : 1;
-            if (maxRun > 48) maxRun = 48;
-            if (maxRun < 1) maxRun = 1;
-            while (j < nReply && (size_t)(j - i) < maxRun &&
-                   sameDest(order[i], order[j]) &&
-                   (riov[order[j]].iov_len == seg ||
-                    (riov[order[j]].iov_len < seg &&
-                     (j + 1 == nReply ||
-                      !sameDest(order[i], order[j + 1])))))
-                ++j;
-            if (replyGso_ && j - i >= 2) {
-                runIovs.clear();
-                for (int k = i; k < j; ++k)
-                    runIovs.push_back(riov[order[k]]);
-                struct msghdr mh {};
-                mh.msg_name = &raddr[order[i]];
-                mh.msg_namelen =
-                    raddr[order[i]].ss_family == AF_INET
-                        ? sizeof(struct sockaddr_in)
-                        : sizeof(struct sockaddr_in6);
-                mh.msg_iov = runIovs.data();
-                mh.msg_iovlen = runIovs.size();
-                char cbuf[CMSG_SPACE(sizeof(uint16_t))] = {0};
-                mh.msg_control = cbuf;
-                mh.msg_controllen = sizeof(cbuf);
-                struct cmsghdr* cm = CMSG_FIRSTHDR(&mh);
-                cm->cmsg_level = SOL_UDP;
-                cm->cmsg_type = UDP_SEGMENT;
-                cm->cmsg_len = CMSG_LEN(sizeof(uint16_t));
-                uint16_t gso = (uint16_t)seg;
-                memcpy(CMSG_DATA(cm), &gso, sizeof(gso));
-                if (sendmsg(udpFd_, &mh, 0) < 0) {
-                    if (errno == EINVAL || errno == EIO ||
-                        errno == ENOTSUP)
-                        replyGso_ = false;  /* disable permanently */
-                    /* ANY failure: the whole run would be lost —
-                     * resend its replies individually */
-                    for (int k = i; k < j; ++k) {
-                        struct msghdr m1 {};
-                        m1.msg_name = mh.msg_name;
-                        m1.msg_namelen = mh.msg_namelen;
-                        m1.msg_iov = &riov[order[k]];
-                        m1.msg_iovlen = 1;
-                        ssize_t r1 = sendmsg(udpFd_, &m1, 0);
-                        (void)r1;
-                    }
-                }
-            } else {
-                /* singles re-packed into a sendmmsg batch */
-                for (int k = i; k < j; ++k) {
-                    memset(&rh[nSingle], 0, sizeof(rh[nSingle]));
-                    rh[nSingle].msg_hdr.msg_iov = &riov[order[k]];
-                    rh[nSingle].msg_hdr.msg_iovlen = 1;
-                    rh[nSingle].msg_hdr.msg_name = &raddr[order[k]];
-                    rh[nSingle].msg_hdr.msg_namelen =
-                        raddr[order[k]].ss_family == AF_INET
-                            ? sizeof(struct sockaddr_in)
-                            : sizeof(struct sockaddr_in6);
-                    nSingle++;
-                }
-            }
-            i = j;
-        }
-        int sent = 0;
-        while (sent < nSingle) {
-            int rv = sendmmsg(udpFd_, rh + sent, nSingle - sent, 0);
-            if (rv <= 0) break;
-            sent += rv;
-        }
-        udpReplies_ += (uint64_t)nReply;
-        nReply = 0;
-    };
-
-    size_t consumed = 0;
-    while (be->in.size() - consumed >= bsock::kHeaderLen) {
-        const uint8_t* h = (const uint8_t*)be->in.data() + consumed;
-        if (h[0] != bsock::kMagic) {
-            backendDown(be.get());
-            return;
-        }
-        uint8_t type = h[1];
-        uint32_t plen = bsock::getU32(h + 2);
-        if (plen > bsock::kMaxPayload) {
-            backendDown(be.get());
-            return;
-        }
-        if (be->in.size() - consumed < bsock::kHeaderLen + plen) break;
-        const uint8_t* payload = h + bsock::kHeaderLen;
-
-        if (type == bsock::FRAME_PONG) {
+        if (f.type == bsock::FRAME_PONG) {
             be->lastPongAt = monotonicMillis();
             be->ok = true;
-        } else if (type == bsock::FRAME_REPLY && plen >= 4) {
-            uint32_t reqId = bsock::getU32(payload);
+        } else if (f.type == bsock::FRAME_REPLY && f.plen >= 4) {
+            uint32_t reqId = bsock::getU32(f.payload);
             PendingSlot* pr = be->slotFor(reqId);
             if (pr->reqId == reqId) {
-                const uint8_t* dns = payload + 4;
-                size_t dnsLen = plen - 4;
+                const uint8_t* dns = f.payload + 4;
+                size_t dnsLen = f.plen - 4;
                 if (pr->tcp) {
                     auto cit = tcpClients_.find(pr->tcpFd);
                     if (cit != tcpClients_.end() &&
@@ -763,39 +756,24 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
                         tcpClientFlush(c);
                     }
                 } else {
-                    if (nReply == kReplyBatch) flushReplies();
-                    socklen_t slen;
-                    if (pr->family == 4) {
-                        auto* sa = (struct sockaddr_in*)&raddr[nReply];
-                        /* zero the FULL storage: the reply sorter
-                         * memcmps whole sockaddr_storage entries */
-                        memset(&raddr[nReply], 0, sizeof(raddr[0]));
-                        sa->sin_family = AF_INET;
-                        sa->sin_port = htons(pr->srcPort);
-                        memcpy(&sa->sin_addr, pr->addr, 4);
-                        slen = sizeof(*sa);
-                    } else {
-                        auto* sa =
-                            (struct sockaddr_in6*)&raddr[nReply];
-                        memset(&raddr[nReply], 0, sizeof(raddr[0]));
-                        sa->sin6_family = AF_INET6;
-                        sa->sin6_port = htons(pr->srcPort);
-                        memcpy(&sa->sin6_addr, pr->addr, 16);
-                        slen = sizeof(*sa);
-                    }
-                    (void)slen;
-                    riov[nReply] = {const_cast<uint8_t*>(dns), dnsLen};
-                    nReply++;
+                    replyRuns_.add(pr->family, pr->addr, pr->srcPort,
+                                   {const_cast<uint8_t*>(dns), dnsLen});
+                    udpReplies_++;
                 }
                 be->replies++;
                 pr->reqId = 0;
                 be->pendingCount--;
             }
         }
-        consumed += bsock::kHeaderLen + plen;
     }
-    flushReplies();
-    be->in.erase(0, consumed);
+    replyRuns_.finish();
+    if (bad) {
+        /* wrong magic or an impossible length: the stream cannot be
+         * resynced */
+        backendDown(be.get());
+        return;
+    }
+    be->in.compact();
 }
 
 Backend* Balancer::chooseLeastLoaded() {
@@ -873,6 +851,7 @@ Backend* Balancer::pickBackendFast(const struct sockaddr_storage& ss) {
                   "remote table overflow; resetting affinity pins");
         remotesFast_.clear();
         remotes_.clear();
+        dropRouteCache();
         for (auto& [id, be] : backendsById_) {
             g_pins.add(be->path, -(int)be->remotes);
             be->remotes = 0;
@@ -901,6 +880,31 @@ Backend* Balancer::pickBackendFast(const struct sockaddr_storage& ss) {
     return be;
 }
 
+Backend* Balancer::routeFor(const struct sockaddr_storage& src) {
+    uint8_t family;
+    const uint8_t* addr;
+    size_t n;
+    if (src.ss_family == AF_INET) {
+        family = 4;
+        addr = (const uint8_t*)&((const struct sockaddr_in*)&src)
+                   ->sin_addr;
+        n = 4;
+    } else {
+        family = 6;
+        addr = (const uint8_t*)&((const struct sockaddr_in6*)&src)
+                   ->sin6_addr;
+        n = 16;
+    }
+    if (routeCache_.be != nullptr && routeCache_.family == family &&
+        memcmp(routeCache_.addr, addr, n) == 0 && routeCache_.be->ok)
+        return routeCache_.be;
+    Backend* be = pickBackendFast(src);
+    routeCache_.be = be;
+    routeCache_.family = family;
+    memcpy(routeCache_.addr, addr, n);
+    return be;
+}
+
 static void ipOf(const struct sockaddr_storage& ss, char* out, size_t n,
                  uint16_t* port, uint8_t* family, uint8_t addr16[16]) {
     memset(addr16, 0, 16);
@@ -921,25 +925,14 @@ static void ipOf(const struct sockaddr_storage& ss, char* out, size_t n,
 
 void Balancer::onUdpReadable() {
     struct mmsghdr* hdrs = rxHdrs_;
-    struct iovec* iovs = rxIovs_;
     struct sockaddr_storage* addrs = rxAddrs_;
 
     while (true) {
-        for (int i = 0; i < kBatch; ++i) {
-            iovs[i] = {rxArena_.data() + (size_t)i * kRxBufSz,
-                       kRxBufSz};
-            memset(&hdrs[i], 0, sizeof(hdrs[i]));
-            hdrs[i].msg_hdr.msg_iov = &iovs[i];
-            hdrs[i].msg_hdr.msg_iovlen = 1;
-            hdrs[i].msg_hdr.msg_name = &addrs[i];
-            hdrs[i].msg_hdr.msg_namelen = sizeof(addrs[i]);
-            hdrs[i].msg_hdr.msg_control = rxCtrl_[i];
-            hdrs[i].msg_hdr.msg_controllen = sizeof(rxCtrl_[i]);
-        }
         int n = recvmmsg(udpFd_, hdrs, kBatch, 0, nullptr);
         if (n <= 0) return;
+        udpRxMsgs_ += (uint64_t)n;
         int64_t expiry = monotonicMillis() + kReplyTtlMs;
-        std::set<Backend*> touched;
+        Touched touched;
         for (int i = 0; i < n; ++i) {
             /* GRO: one message may be several equal-size datagrams;
              * the segment size arrives as a UDP_GRO cmsg */
@@ -954,24 +947,30 @@ void Balancer::onUdpReadable() {
                     if (g > 0) seg = g;
                 }
             }
+            /* what the kernel overwrote, ready for the next call */
+            hdrs[i].msg_hdr.msg_namelen = sizeof(addrs[i]);
+            hdrs[i].msg_hdr.msg_controllen = sizeof(rxCtrl_[i]);
+            hdrs[i].msg_hdr.msg_flags = 0;
+            /* routed once per message: every segment of it has the
+             * same source. Nothing in the segment loop can take a
+             * backend down (flushes wait for the end of the batch). */
+            Backend* be = routeFor(addrs[i]);
             const uint8_t* base = rxArena_.data() + (size_t)i * kRxBufSz;
             size_t total = hdrs[i].msg_len;
             for (size_t off = 0; off < total; off += seg) {
                 size_t dnsLen = std::min(seg, total - off);
-                handleUdpQuery(base + off, dnsLen, addrs[i], expiry,
-                               touched);
+                handleUdpQuery(base + off, dnsLen, addrs[i], expiry, be);
             }
+            if (be != nullptr) touch(touched, be);
         }
-        for (Backend* be : touched) backendFlush(be);
+        flushTouched(touched);
         if (n < kBatch) return;
     }
 }
 
 void Balancer::handleUdpQuery(const uint8_t* dns, size_t dnsLen,
                               const struct sockaddr_storage& src,
-                              int64_t expiry,
-                              std::set<Backend*>& touched) {
-    Backend* be = pickBackendFast(src);
+                              int64_t expiry, Backend* be) {
     udpQueries_++;
     if (be == nullptr) {
         drops_++;
@@ -1036,7 +1035,6 @@ void Balancer::handleUdpQuery(const uint8_t* dns, size_t dnsLen,
     o.append((const char*)head, sizeof(head));
     o.append((const char*)dns, dnsLen);
     be->queries++;
-    touched.insert(be);
 }
 
 void Balancer::onTcpAccept() {
@@ -1180,6 +1178,12 @@ Json Balancer::snapshot() const {
     out.set("udp_queries", Json((int64_t)udpQueries_));
     out.set("udp_replies", Json((int64_t)udpReplies_));
     out.set("drops", Json((int64_t)drops_));
+    out.set("reply_runs", Json((int64_t)replyRuns_.runs()));
+    out.set("reply_run_segments",
+            Json((int64_t)replyRuns_.runSegments()));
+    out.set("reply_singles", Json((int64_t)replyRuns_.singles()));
+    out.set("backend_reads", Json((int64_t)backendReads_));
+    out.set("udp_rx_msgs", Json((int64_t)udpRxMsgs_));
     return out;
 }
 
@@ -1196,6 +1200,11 @@ void Balancer::onStatsAccept() {
         std::map<std::string, Json> byPath;      // merged backends
         JsonArray remotes;
         int64_t udpQ = 0, udpR = 0, drops = 0;
+        static const char* const kHot[] = {
+            "reply_runs", "reply_run_segments", "reply_singles",
+            "backend_reads", "udp_rx_msgs"};
+        int64_t hot[5] = {0, 0, 0, 0, 0};
+        JsonArray perWorker;
         int workers = 0;
         for (const std::string& frag : g_stats.all()) {
             auto parsed = Json::parse(frag);
@@ -1204,6 +1213,17 @@ void Balancer::onStatsAccept() {
             udpQ += parsed->get("udp_queries").asInt();
             udpR += parsed->get("udp_replies").asInt();
             drops += parsed->get("drops").asInt();
+            /* the hot-path counters merged, and per worker as well:
+             * run length and read size differ between shards */
+            Json pw = Json::object();
+            pw.set("udp_queries", parsed->get("udp_queries"));
+            pw.set("udp_replies", parsed->get("udp_replies"));
+            pw.set("drops", parsed->get("drops"));
+            for (int k = 0; k < 5; ++k) {
+                hot[k] += parsed->get(kHot[k]).asInt();
+                pw.set(kHot[k], parsed->get(kHot[k]));
+            }
+            perWorker.push_back(std::move(pw));
             for (const auto& r : parsed->get("remotes").items())
                 remotes.push_back(r);
             for (const auto& b : parsed->get("backends").items()) {
@@ -1237,6 +1257,8 @@ void Balancer::onStatsAccept() {
         out.set("udp_queries", Json(udpQ));
         out.set("udp_replies", Json(udpR));
         out.set("drops", Json(drops));
+        for (int k = 0; k < 5; ++k) out.set(kHot[k], Json(hot[k]));
+        out.set("per_worker", Json(std::move(perWorker)));
         out.set("workers", Json((int64_t)workers));
         std::string s = out.dump();
         s.push_back('\n');

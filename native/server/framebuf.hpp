@@ -25,8 +25,11 @@ namespace bamd {
 class FrameBuf {
   public:
     /* resting capacity: one per-event read quota plus a small partial
-     * frame; larger frames grow the buffer, compact() shrinks it back */
+     * frame; larger frames grow the buffer, compact() shrinks it back.
+     * An owner that reads more per event passes its own. */
     static constexpr size_t kRestCap = 160 * 1024;
+
+    explicit FrameBuf(size_t restCap = kRestCap) : restCap_(restCap) {}
 
     /* unparsed bytes */
     const uint8_t* data() const { return buf_.get() + rd_; }
@@ -44,12 +47,15 @@ class FrameBuf {
     /* drop n parsed bytes from the front (cursor move only) */
     void consume(size_t n) { rd_ += n; }
 
+    /* forget everything received (the connection is gone) */
+    void clear() { rd_ = wr_ = 0; }
+
     /* Once per event, after the parse loop: bring the unparsed rest to
      * the front and give back memory a large frame made us take. */
     void compact() {
         size_t left = wr_ - rd_;
-        if (cap_ > kRestCap && left <= kRestCap / 4) {
-            move(kRestCap);
+        if (cap_ > restCap_ && left <= restCap_ / 4) {
+            move(restCap_);
             return;
         }
         if (rd_ != 0) {
@@ -70,7 +76,7 @@ class FrameBuf {
             return;
         }
         size_t need = left + want;
-        size_t ncap = cap_ == 0 ? kRestCap : cap_ * 2;
+        size_t ncap = cap_ == 0 ? restCap_ : cap_ * 2;
         if (ncap < need) ncap = need;
         move(ncap);
     }
@@ -88,6 +94,7 @@ class FrameBuf {
     }
 
     std::unique_ptr<uint8_t[]> buf_;
+    size_t restCap_;
     size_t cap_ = 0;
     size_t rd_ = 0;  /* parse cursor */
     size_t wr_ = 0;  /* end of received bytes */

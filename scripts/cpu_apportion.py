@@ -6,7 +6,15 @@ consumed per component — the denominator that bounds qps on the
 quota-capped bench boxes (profiles/SCALING.md round 2).
 
 usage: cpu_apportion.py [--procs 8] [--workers 8] [--threads 6]
-                        [--window 256] [--ramp 2]
+                        [--window 256] [--ramp 2] [--tag NAME]
+
+Every component is reported as total cores and split into user and
+system time. For the balancer the cost per query (core-us, user and
+system) and the shape of its hot path over the window are added from
+its stats socket: mean reply-run length, share of replies that left
+singly, replies per backend read, queries per received UDP message.
+BALANCER_BIN selects the balancer binary (binder_amd/harness.py), so a
+parent build and a new one can alternate inside one box visit.
 
 The generator is given far more queries than any window can use: a
 budget that runs out inside the window (100 M did, once the chain
@@ -33,7 +41,7 @@ def cpu_of(pid):
     try:
         parts = open(f"/proc/{pid}/stat").read().rsplit(") ", 1)[1]
         f = parts.split()
-        return (int(f[11]) + int(f[12])) / HZ  # utime+stime (s)
+        return int(f[11]) / HZ, int(f[12]) / HZ  # utime, stime (s)
     except (OSError, IndexError, ValueError):
         return None
 
@@ -49,6 +57,8 @@ def main():
     ap.add_argument("--ramp", type=float, default=2.0,
                     help="seconds of load before the sampling window")
     ap.add_argument("--no-gso", action="store_true")
+    ap.add_argument("--tag", default=None,
+                    help="copied into the output row (e.g. the build)")
     args = ap.parse_args()
 
     from binder_amd.harness import free_port, NativeZkd
@@ -95,14 +105,47 @@ def main():
                "window": args.window, "ramp_s": args.ramp, "gso": not args.no_gso,
                "qps": round((st1["udp_replies"] -
                              st0["udp_replies"]) / dt)}
+        if args.tag:
+            out["tag"] = args.tag
         total = 0.0
+        split = {}
         for k in pids:
-            cores = sum((a - b) for a, b in
-                        zip(after[k], before[k])
-                        if a is not None and b is not None) / dt
-            out[k + "_cores"] = round(cores, 2)
-            total += cores
+            pairs = [(a, b) for a, b in zip(after[k], before[k])
+                     if a is not None and b is not None]
+            user = sum(a[0] - b[0] for a, b in pairs) / dt
+            syst = sum(a[1] - b[1] for a, b in pairs) / dt
+            split[k] = (user, syst)
+            out[k + "_cores"] = round(user + syst, 2)
+            out[k + "_user_cores"] = round(user, 2)
+            out[k + "_sys_cores"] = round(syst, 2)
+            total += user + syst
         out["total_cores"] = round(total, 2)
+        if out["qps"] > 0:
+            user, syst = split["balancer"]
+            per_q = 1e6 / out["qps"]  # cores -> core-us per query
+            out["balancer_core_us_per_query"] = round(
+                (user + syst) * per_q, 4)
+            out["balancer_user_us_per_query"] = round(user * per_q, 4)
+            out["balancer_sys_us_per_query"] = round(syst * per_q, 4)
+        # hot-path shape over the window (absent from older balancers)
+        d = {k: st1[k] - st0[k] for k in
+             ("udp_queries", "udp_replies", "reply_runs",
+              "reply_run_segments", "reply_singles", "backend_reads",
+              "udp_rx_msgs") if k in st1 and k in st0}
+        if "reply_runs" in d:
+            out.update(d)
+            if d["reply_runs"]:
+                out["mean_run_len"] = round(
+                    d["reply_run_segments"] / d["reply_runs"], 2)
+            if d["udp_replies"]:
+                out["singles_share"] = round(
+                    d["reply_singles"] / d["udp_replies"], 4)
+            if d["backend_reads"]:
+                out["replies_per_backend_read"] = round(
+                    d["udp_replies"] / d["backend_reads"], 1)
+            if d["udp_rx_msgs"]:
+                out["queries_per_udp_msg"] = round(
+                    d["udp_queries"] / d["udp_rx_msgs"], 2)
         try:
             q, p = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
             out["quota_cores"] = (int(q) // int(p)
