@@ -140,6 +140,30 @@ $(BUILD)/replyruns_check: native/balancer/replyruns_check_main.cpp \
 check-replyruns: $(BUILD)/replyruns_check
 	$(BUILD)/replyruns_check 1 300
 
+# Sanitizer runs of the shared-memory byte rings (shmpipe.hpp) in a
+# stand-alone program whose producer and consumer are two of its own
+# threads: once under ASan+UBSan, once under ThreadSanitizer. Random
+# chunks through a 4 KiB ring, full/partial/resume, the park/doorbell
+# handshake over 100000 handoffs with bounded waits, corrupted control
+# blocks. Host-only, CPU-only.
+SHMPIPE_CHECK_DEPS := native/common/shmpipe_check_main.cpp \
+	native/common/shmpipe.hpp
+
+$(BUILD)/shmpipe_check_asan: $(SHMPIPE_CHECK_DEPS)
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@ -lpthread
+
+$(BUILD)/shmpipe_check_tsan: $(SHMPIPE_CHECK_DEPS)
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=thread $< -o $@ -lpthread
+
+check-shmpipe: $(BUILD)/shmpipe_check_asan $(BUILD)/shmpipe_check_tsan
+	$(BUILD)/shmpipe_check_asan 1 100000
+	$(BUILD)/shmpipe_check_tsan 1 100000
+
 # ThreadSanitizer run of the serving-thread pool: binderd itself (a daemon
 # with its own main) built with -fsanitize=thread into $(BUILD)/tsan, and
 # the pool's tests plus the two suites that pin reply order and ingress
@@ -188,4 +212,4 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
-	check-replyruns check-serve-threads release
+	check-replyruns check-shmpipe check-serve-threads release

@@ -18,7 +18,9 @@
  *     consumed by `binder-amd balstat`.
  *
  * Flags: -p port (default 53), -H host, -s socket-dir (default
- * /var/run/binder/sockets), -S stats-socket path, -r rescan interval ms.
+ * /var/run/binder/sockets), -S stats-socket path, -r rescan interval ms,
+ * -M 0|1 offer backends shared-memory rings for the bsock1 hop (default
+ * 1; environment BINDER_BAL_SHM).
  */
 #include <arpa/inet.h>
 #include <dirent.h>
@@ -26,6 +28,7 @@
 #include <netinet/udp.h>
 #include <signal.h>
 #include <sys/epoll.h>
+#include <sys/eventfd.h>
 #include <sys/signalfd.h>
 #include <sys/socket.h>
 #include <sys/stat.h>
@@ -49,6 +52,7 @@
 #include "../common/json.hpp"
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
+#include "../common/shmpipe.hpp"
 #include "../server/framebuf.hpp"
 #include "protocol.hpp"
 #include "replyruns.hpp"
@@ -181,6 +185,11 @@ static_assert(sizeof(PendingSlot) <= 32, "keep the ring compact");
  * tiny values let tests exercise the overwrite accounting). */
 size_t g_pendingSlots = 32768;
 
+/* offer shared-memory rings to backends (-M, BINDER_BAL_SHM), and the
+ * size of each ring (BINDER_BAL_SHM_RING; for tests) */
+bool g_shmOn = true;
+size_t g_shmRing = shm::kDefaultRing;
+
 /* bounded batch per backend event (level-triggered epoll re-fires):
  * draining a many-MB reply backlog in one go stalls the worker's other
  * duties for milliseconds */
@@ -212,6 +221,18 @@ struct Backend {
     size_t outOff = 0;  /* consumed prefix of `out` (flush cursor) */
     size_t sweepCursor = 0;  /* incremental pending-expiry scan */
     size_t remotes = 0;
+
+    /* Shared-memory rings for this connection (protocol.hpp, types
+     * 5-7). shmOffered: the region exists and the offer went out.
+     * rxShm: SHM_OK seen, replies are taken from the reply ring.
+     * streamEnd: end of the SHM_GO frame in `out`; bytes before it
+     * still go to the socket, and once they have, txShm is set and
+     * everything after goes to the query ring. */
+    shm::Link shm;
+    bool shmOffered = false;
+    bool rxShm = false;
+    bool txShm = false;
+    size_t streamEnd = 0;
 
     PendingSlot* slotFor(uint32_t reqId) {
         if (!pending) {
@@ -259,7 +280,13 @@ class Balancer {
     void connectBackend(Backend* be);
     void backendDown(Backend* be);
     void onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev);
+    void onBackendBell(std::shared_ptr<Backend> be);
+    void serveBackend(Backend* be, bool fromRing);
+    void offerShm(Backend* be);
+    void dropShm(Backend* be);
+    EventLoop::Park beforePark(bool park);
     void backendFlush(Backend* be);
+    void flushToRing(Backend* be);
     Backend* pickBackend(const std::string& remoteIp);
     Backend* pickBackendFast(const struct sockaddr_storage& ss);
     Backend* chooseLeastLoaded();
@@ -303,6 +330,10 @@ class Balancer {
      * messages received (a GRO message counts once however many
      * queries it carries) */
     uint64_t backendReads_ = 0, udpRxMsgs_ = 0;
+    /* doorbells this worker rang (eventfd writes), and takes from a
+     * reply ring that returned data; doorbells per drain is what the
+     * rings save over the stream, where every batch is a wakeup */
+    uint64_t shmDoorbells_ = 0, shmDrains_ = 0;
 
     static constexpr size_t kMaxRemotes = 262144;
     static constexpr size_t kMaxPending = 16384;
@@ -466,6 +497,9 @@ bool Balancer::start() {
     }
     loop_->addFd(udpFd_, EPOLLIN, [this](uint32_t) { onUdpReadable(); });
     loop_->addFd(tcpFd_, EPOLLIN, [this](uint32_t) { onTcpAccept(); });
+    if (g_shmOn)
+        loop_->setBeforePark(
+            [this](bool park) { return beforePark(park); });
 
     if (!statsPath_.empty()) {
         statsFd_ = socket(AF_UNIX, SOCK_STREAM | SOCK_NONBLOCK |
@@ -570,6 +604,73 @@ void Balancer::connectBackend(Backend* be) {
     loop_->addFd(fd, EPOLLIN, [this, self](uint32_t ev) {
         onBackendEvent(self, ev);
     });
+    /* a UNIX connect that returned 0 is complete: the offer can go now,
+     * ahead of every query */
+    if (g_shmOn && rv == 0) offerShm(be);
+}
+
+/* Make the region and the doorbells and send SHM_OFFER with the three
+ * descriptors. Any failure leaves the connection on the stream. */
+void Balancer::offerShm(Backend* be) {
+    int fds[bsock::kShmOfferFds] = {-1, -1, -1};
+    fds[0] = be->shm.region.create(g_shmRing);
+    if (fds[0] >= 0) {
+        fds[1] = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC);
+        fds[2] = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC);
+    }
+    bool sent = false;
+    if (fds[1] >= 0 && fds[2] >= 0) {
+        uint8_t frame[bsock::kHeaderLen + bsock::kShmOfferLen];
+        auto put32 = [](uint8_t* p, uint32_t v) {
+            p[0] = (uint8_t)v;
+            p[1] = (uint8_t)(v >> 8);
+            p[2] = (uint8_t)(v >> 16);
+            p[3] = (uint8_t)(v >> 24);
+        };
+        frame[0] = bsock::kMagic;
+        frame[1] = bsock::FRAME_SHM_OFFER;
+        put32(frame + 2, (uint32_t)bsock::kShmOfferLen);
+        put32(frame + 6, shm::kVersion);
+        put32(frame + 10, (uint32_t)g_shmRing);
+        put32(frame + 14, (uint32_t)shm::kDataOff);
+        struct iovec iov = {frame, sizeof(frame)};
+        alignas(struct cmsghdr) char cbuf[CMSG_SPACE(sizeof(fds))] = {0};
+        struct msghdr mh {};
+        mh.msg_iov = &iov;
+        mh.msg_iovlen = 1;
+        mh.msg_control = cbuf;
+        mh.msg_controllen = sizeof(cbuf);
+        struct cmsghdr* cm = CMSG_FIRSTHDR(&mh);
+        cm->cmsg_level = SOL_SOCKET;
+        cm->cmsg_type = SCM_RIGHTS;
+        cm->cmsg_len = CMSG_LEN(sizeof(fds));
+        memcpy(CMSG_DATA(cm), fds, sizeof(fds));
+        /* 18 bytes into an empty send buffer: all or nothing */
+        sent = sendmsg(be->fd, &mh, MSG_NOSIGNAL) == (ssize_t)sizeof(frame);
+    }
+    if (fds[0] >= 0) close(fds[0]);  /* mapped, and sent or useless */
+    if (!sent) {
+        log_.debug({{"path", Json(be->path)}},
+                   "no shared-memory offer; staying on the stream");
+        if (fds[1] >= 0) close(fds[1]);
+        if (fds[2] >= 0) close(fds[2]);
+        be->shm.close();
+        return;
+    }
+    be->shm.wakePeer = fds[1];
+    be->shm.wakeMe = fds[2];
+    be->shm.attachEnds(true);
+    be->shmOffered = true;
+    auto self = backendsById_[be->id];
+    loop_->addFd(be->shm.wakeMe, EPOLLIN | EPOLLET,
+                 [this, self](uint32_t) { onBackendBell(self); });
+}
+
+void Balancer::dropShm(Backend* be) {
+    if (be->shmOffered) loop_->delFd(be->shm.wakeMe);
+    be->shm.close();
+    be->shmOffered = be->rxShm = be->txShm = false;
+    be->streamEnd = 0;
 }
 
 void Balancer::backendDown(Backend* be) {
@@ -578,6 +679,7 @@ void Balancer::backendDown(Backend* be) {
         close(be->fd);
         be->fd = -1;
     }
+    dropShm(be);
     be->ok = false;
     dropRouteCache();
     be->in.clear();
@@ -653,10 +755,52 @@ void Balancer::backendDown(Backend* be) {
     }
 }
 
+/* Query bytes into the ring: what fits now; the rest stays in `out`
+ * and the backend rings our doorbell when it has made room. */
+void Balancer::flushToRing(Backend* be) {
+    bool wrote = false;
+    be->writeBlocked = false;
+    while (be->outOff < be->out.size()) {
+        size_t n = be->shm.tx.write(be->out.data() + be->outOff,
+                                    be->out.size() - be->outOff);
+        be->outOff += n;
+        if (n != 0) wrote = true;
+        if (be->outOff >= be->out.size()) break;
+        if (be->shm.tx.bad()) {
+            log_.warn({{"path", Json(be->path)}},
+                      "backend corrupted the query ring");
+            backendDown(be);
+            return;
+        }
+        if (be->shm.tx.waitForSpace()) {
+            be->writeBlocked = true;
+            break;
+        }
+    }
+    if (wrote && be->shm.tx.consumerNeedsWake()) {
+        shm::ringDoorbell(be->shm.wakePeer);
+        shmDoorbells_++;
+    }
+    if (be->outOff >= be->out.size()) {
+        be->out.clear();
+        be->outOff = 0;
+    } else if (be->outOff > (1u << 20)) {
+        be->out.erase(0, be->outOff);
+        be->outOff = 0;
+    }
+}
+
 void Balancer::backendFlush(Backend* be) {
-    while (be->outOff < be->out.size() && be->fd >= 0) {
+    if (be->txShm) {
+        if (be->fd >= 0) flushToRing(be);
+        return;
+    }
+    /* with a SHM_GO queued, the stream gets the bytes up to its end */
+    while (be->fd >= 0) {
+        size_t end = be->streamEnd != 0 ? be->streamEnd : be->out.size();
+        if (be->outOff >= end) break;
         ssize_t nw = write(be->fd, be->out.data() + be->outOff,
-                           be->out.size() - be->outOff);
+                           end - be->outOff);
         if (nw > 0) {
             be->outOff += (size_t)nw;
             continue;
@@ -667,6 +811,7 @@ void Balancer::backendFlush(Backend* be) {
              * O(n) memmove-per-write of erase(0, nw)) */
             if (be->outOff > (1u << 20)) {
                 be->out.erase(0, be->outOff);
+                if (be->streamEnd != 0) be->streamEnd -= be->outOff;
                 be->outOff = 0;
             }
             if (!be->writeBlocked) {
@@ -678,13 +823,21 @@ void Balancer::backendFlush(Backend* be) {
         backendDown(be);
         return;
     }
+    if (be->fd < 0) return;
+    if (be->writeBlocked) {
+        be->writeBlocked = false;
+        loop_->modFd(be->fd, EPOLLIN);
+    }
+    if (be->streamEnd != 0 && be->outOff >= be->streamEnd) {
+        /* SHM_GO is on the wire: the ring from here on */
+        be->streamEnd = 0;
+        be->txShm = true;
+        flushToRing(be);
+        return;
+    }
     if (be->outOff >= be->out.size()) {
         be->out.clear();
         be->outOff = 0;
-    }
-    if (be->writeBlocked && be->fd >= 0) {
-        be->writeBlocked = false;
-        loop_->modFd(be->fd, EPOLLIN);
     }
 }
 
@@ -697,12 +850,62 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
     }
     if (ev & EPOLLOUT) backendFlush(be.get());
     if (!(ev & EPOLLIN) || be->fd < 0) return;
+    if (be->rxShm) {
+        /* SHM_OK was the backend's last word on the stream: all that
+         * can show up here now is its end, or a peer gone wrong */
+        char junk[64];
+        ssize_t nr = read(be->fd, junk, sizeof(junk));
+        if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return;
+        log_.warn({{"path", Json(be->path)}}, "backend closed connection");
+        backendDown(be.get());
+        return;
+    }
+    serveBackend(be.get(), false);
+}
 
+/* the backend's doorbell: replies in the ring, or room in the query
+ * ring we were waiting for (edge-triggered; the eventfd is not read) */
+void Balancer::onBackendBell(std::shared_ptr<Backend> be) {
+    if (be->fd < 0 || !be->shmOffered) return;
+    if (be->txShm && be->writeBlocked) backendFlush(be.get());
+    if (be->fd >= 0 && be->rxShm) serveBackend(be.get(), true);
+}
+
+/* The loop's hook (loop.hpp). Every round: take what the reply rings
+ * hold - under load there is something, and nobody had to wake us for
+ * it. Before a real sleep: tell the backends, and look once more. */
+EventLoop::Park Balancer::beforePark(bool park) {
+    EventLoop::Park out = EventLoop::Park::NoRings;
+    for (auto& [id, be] : backendsById_) {
+        if (!be->rxShm || be->fd < 0) continue;
+        if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
+        if (park) {
+            if (!be->shm.rx.park()) out = EventLoop::Park::Work;
+        } else if (be->shm.rx.readable() != 0 || be->shm.rx.bad()) {
+            serveBackend(be.get(), true);
+            out = EventLoop::Park::Work;
+        }
+    }
+    return out;
+}
+
+void Balancer::serveBackend(Backend* be, bool fromRing) {
     /* straight into the frame buffer's tail; a read that returns
      * less than was asked for has drained the socket, so the EAGAIN
-     * read that used to end every event is not made */
+     * read that used to end every event is not made. A ring is drained
+     * the same way, to the same quota. */
     size_t got = 0;
     while (got < kMaxReadPerEvent) {
+        if (fromRing) {
+            size_t n = be->shm.rx.read(be->in.tail(kReadChunk), kReadChunk);
+            if (n == 0) break;
+            be->in.commit(n);
+            got += n;
+            backendReads_++;
+            shmDrains_++;
+            if (n < kReadChunk) break;
+            continue;
+        }
         ssize_t nr = read(be->fd, be->in.tail(kReadChunk), kReadChunk);
         if (nr > 0) {
             be->in.commit((size_t)nr);
@@ -713,8 +916,21 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
         }
         if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
         log_.warn({{"path", Json(be->path)}}, "backend closed connection");
-        backendDown(be.get());
+        backendDown(be);
         return;
+    }
+    if (fromRing) {
+        if (be->shm.rx.bad()) {
+            log_.warn({{"path", Json(be->path)}},
+                      "backend corrupted the reply ring");
+            backendDown(be);
+            return;
+        }
+        if (got == 0) return;
+        if (be->shm.rx.producerNeedsWake()) {
+            shm::ringDoorbell(be->shm.wakePeer);
+            shmDoorbells_++;
+        }
     }
 
     /* Walk the complete frames. UDP replies are filed into reply runs
@@ -727,7 +943,7 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
      * reads of the event are done (above), and nothing may move or
      * reuse that buffer - no tail(), compact(), clear(), so no
      * backendDown() either - until replyRuns_.finish() has run. */
-    bool bad = false;
+    bool bad = false, sawOk = false;
     for (;;) {
         bsock::FrameView f;
         bsock::FrameStatus st = bsock::nextFrame(be->in, f);
@@ -739,6 +955,17 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
         if (f.type == bsock::FRAME_PONG) {
             be->lastPongAt = monotonicMillis();
             be->ok = true;
+        } else if (f.type == bsock::FRAME_SHM_OK) {
+            if (!be->shmOffered || be->rxShm) {
+                bad = true;  /* nothing was offered, or twice */
+                break;
+            }
+            /* the backend's replies continue in the ring; ours follow
+             * this SHM_GO there, once the stream has carried it */
+            be->rxShm = true;
+            sawOk = true;
+            bsock::appendFrame(be->out, bsock::FRAME_SHM_GO, "");
+            be->streamEnd = be->out.size();
         } else if (f.type == bsock::FRAME_REPLY && f.plen >= 4) {
             uint32_t reqId = bsock::getU32(f.payload);
             PendingSlot* pr = be->slotFor(reqId);
@@ -767,13 +994,17 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
         }
     }
     replyRuns_.finish();
+    /* SHM_OK ends the stream: a partial frame behind it can never be
+     * completed */
+    if (sawOk && be->in.size() != 0) bad = true;
     if (bad) {
         /* wrong magic or an impossible length: the stream cannot be
          * resynced */
-        backendDown(be.get());
+        backendDown(be);
         return;
     }
     be->in.compact();
+    if (sawOk) backendFlush(be);
 }
 
 Backend* Balancer::chooseLeastLoaded() {
@@ -1164,6 +1395,9 @@ Json Balancer::snapshot() const {
         b.set("replies", Json((int64_t)be->replies));
         b.set("pending", Json((int64_t)be->pendingCount));
         b.set("overwrites", Json((int64_t)be->overwrites));
+        b.set("transport",
+              Json(std::string(be->rxShm && be->txShm ? "shm"
+                                                      : "stream")));
         bes.push_back(std::move(b));
     }
     out.set("backends", Json(std::move(bes)));
@@ -1184,6 +1418,8 @@ Json Balancer::snapshot() const {
     out.set("reply_singles", Json((int64_t)replyRuns_.singles()));
     out.set("backend_reads", Json((int64_t)backendReads_));
     out.set("udp_rx_msgs", Json((int64_t)udpRxMsgs_));
+    out.set("shm_doorbells", Json((int64_t)shmDoorbells_));
+    out.set("shm_drains", Json((int64_t)shmDrains_));
     return out;
 }
 
@@ -1202,8 +1438,10 @@ void Balancer::onStatsAccept() {
         int64_t udpQ = 0, udpR = 0, drops = 0;
         static const char* const kHot[] = {
             "reply_runs", "reply_run_segments", "reply_singles",
-            "backend_reads", "udp_rx_msgs"};
-        int64_t hot[5] = {0, 0, 0, 0, 0};
+            "backend_reads", "udp_rx_msgs", "shm_doorbells",
+            "shm_drains"};
+        constexpr int kNHot = 7;
+        int64_t hot[kNHot] = {0, 0, 0, 0, 0, 0, 0};
         JsonArray perWorker;
         int workers = 0;
         for (const std::string& frag : g_stats.all()) {
@@ -1219,7 +1457,7 @@ void Balancer::onStatsAccept() {
             pw.set("udp_queries", parsed->get("udp_queries"));
             pw.set("udp_replies", parsed->get("udp_replies"));
             pw.set("drops", parsed->get("drops"));
-            for (int k = 0; k < 5; ++k) {
+            for (int k = 0; k < kNHot; ++k) {
                 hot[k] += parsed->get(kHot[k]).asInt();
                 pw.set(kHot[k], parsed->get(kHot[k]));
             }
@@ -1246,6 +1484,9 @@ void Balancer::onStatsAccept() {
                                b.get("overwrites").asInt()));
                     m.set("ok", Json(m.get("ok").asBool() ||
                                      b.get("ok").asBool()));
+                    /* "shm" only if every worker's connection is */
+                    if (b.get("transport").asString() != "shm")
+                        m.set("transport", b.get("transport"));
                 }
             }
         }
@@ -1257,7 +1498,8 @@ void Balancer::onStatsAccept() {
         out.set("udp_queries", Json(udpQ));
         out.set("udp_replies", Json(udpR));
         out.set("drops", Json(drops));
-        for (int k = 0; k < 5; ++k) out.set(kHot[k], Json(hot[k]));
+        for (int k = 0; k < kNHot; ++k)
+            out.set(kHot[k], Json(hot[k]));
         out.set("per_worker", Json(std::move(perWorker)));
         out.set("workers", Json((int64_t)workers));
         std::string s = out.dump();
@@ -1339,8 +1581,17 @@ int main(int argc, char** argv) {
     int rescanMs = 1000;
     int workers = 1;
     int c;
-    while ((c = getopt(argc, argv, "hp:H:s:S:r:w:q:")) != -1) {
+    /* environment first, so that one build can be run both ways; the
+     * flag, when given, wins */
+    if (const char* e = getenv("BINDER_BAL_SHM"); e && *e)
+        g_shmOn = atoi(e) != 0;
+    if (const char* e = getenv("BINDER_BAL_SHM_RING"); e && *e) {
+        size_t v = (size_t)strtoull(e, nullptr, 10);
+        if (shm::validRingBytes(v)) g_shmRing = v;
+    }
+    while ((c = getopt(argc, argv, "hp:H:s:S:r:w:q:M:")) != -1) {
         switch (c) {
+        case 'M': g_shmOn = atoi(optarg) != 0; break;
         case 'q': {
             size_t v = (size_t)strtoull(optarg, nullptr, 10);
             size_t p2 = 1;
@@ -1359,7 +1610,7 @@ int main(int argc, char** argv) {
             fprintf(stderr,
                     "usage: binder-balancer [-p port] [-H host] "
                     "[-s socket-dir] [-S stats-socket] [-r rescan-ms] "
-                    "[-w workers] [-q ring-slots]\n");
+                    "[-w workers] [-q ring-slots] [-M 0|1]\n");
             return c == 'h' ? 0 : 1;
         }
     }

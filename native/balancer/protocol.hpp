@@ -14,6 +14,19 @@
  *   REPLY  (2): req_id(u32le) dns_message
  *   PING   (3): empty          (balancer -> backend health probe)
  *   PONG   (4): empty
+ *   SHM_OFFER (5): version(u32le) ring_bytes(u32le) data_offset(u32le)
+ *               (balancer -> backend, with descriptors; see below)
+ *   SHM_OK (6): empty          (backend -> balancer: last reply bytes on
+ *                               the stream, replies follow in the ring)
+ *   SHM_GO (7): empty          (balancer -> backend: last query bytes on
+ *                               the stream, queries follow in the ring)
+ *
+ * Types 5-7 move an established connection from the stream onto a pair
+ * of shared-memory byte rings (common/shmpipe.hpp) that carry the very
+ * same frames. A peer that does not know them skips type 5 like any
+ * unknown type, never answers, and the connection stays on the stream.
+ * The socket stays open either way: its EOF/HUP is how a dead peer is
+ * noticed.
  *
  * One persistent stream connection per backend, queries multiplexed by
  * req_id. Backend presence = socket exists in the socket directory and
@@ -34,7 +47,15 @@ enum : uint8_t {
     FRAME_REPLY = 2,
     FRAME_PING = 3,
     FRAME_PONG = 4,
+    FRAME_SHM_OFFER = 5,
+    FRAME_SHM_OK = 6,
+    FRAME_SHM_GO = 7,
 };
+/* SHM_OFFER payload; three descriptors ride on its first byte as
+ * SCM_RIGHTS, in this order: the region's memfd, the eventfd that wakes
+ * the backend, the eventfd that wakes the balancer */
+constexpr size_t kShmOfferLen = 4 + 4 + 4;
+constexpr int kShmOfferFds = 3;
 constexpr size_t kHeaderLen = 6;
 constexpr size_t kQueryHeadLen = 4 + 1 + 1 + 2 + 16;
 constexpr uint32_t kMaxPayload = 1 << 20;

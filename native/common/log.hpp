@@ -55,6 +55,9 @@ class Logger {
     void warn(const std::string& m) const { log(LogLevel::Warn, m); }
     void error(const std::string& m) const { log(LogLevel::Error, m); }
     void fatal(const std::string& m) const { log(LogLevel::Fatal, m); }
+    void debug(const JsonObject& extra, const std::string& m) const {
+        log(LogLevel::Debug, m, extra);
+    }
     void info(const JsonObject& extra, const std::string& m) const {
         log(LogLevel::Info, m, extra);
     }

@@ -67,7 +67,10 @@ void EventLoop::addFd(int fd, uint32_t events, FdCallback cb) {
     if (epoll_ctl(epfd_, EPOLL_CTL_ADD, fd, &ev) != 0)
         throw std::runtime_error(std::string("epoll_ctl add: ") +
                                  strerror(errno));
-    fds_[fd] = FdReg{gen, std::move(cb)};
+    FdReg& reg = fds_[fd];
+    retire(reg);
+    reg.gen = gen;
+    reg.cb = std::make_unique<FdCallback>(std::move(cb));
     wakeIfForeign();
 }
 
@@ -84,7 +87,10 @@ void EventLoop::modFd(int fd, uint32_t events) {
 
 void EventLoop::delFd(int fd) {
     epoll_ctl(epfd_, EPOLL_CTL_DEL, fd, nullptr);
-    fds_.erase(fd);
+    auto it = fds_.find(fd);
+    if (it == fds_.end()) return;
+    retire(it->second);
+    fds_.erase(it);
 }
 
 uint64_t EventLoop::addTimer(int64_t delayMs, TimerCallback cb) {
@@ -134,8 +140,20 @@ void EventLoop::runOnce(int64_t maxWaitMs) {
         for (auto& t : tasks) t();
     }
 
+    /* what cannot wake us by itself is looked at every round */
+    Park ring = beforePark_ ? beforePark_(false) : Park::NoRings;
+    bool busy = ring == Park::Work;
+
     int64_t wait = nextTimerDelay();
     if (wait < 0 || wait > maxWaitMs) wait = maxWaitMs;
+    if (ring == Park::NoRings) {
+        hadWork_ = false;  /* nothing to poll for: as without a hook */
+    } else if (busy || hadWork_) {
+        /* sleep only after a round that found nothing anywhere */
+        wait = 0;
+    } else if (wait != 0 && beforePark_(true) == Park::Work) {
+        wait = 0;  /* said so first (loop.hpp), and something slipped in */
+    }
 
     struct epoll_event evs[64];
     if (lk.owns_lock()) lk.unlock();
@@ -143,21 +161,26 @@ void EventLoop::runOnce(int64_t maxWaitMs) {
     int waitErrno = errno;
     if (dispatchLock_ != nullptr) lk.lock();
     errno = waitErrno;
+    hadWork_ = ring != Park::NoRings && (busy || n > 0);
     if (n < 0) {
         if (errno == EINTR) return;
         throw std::runtime_error(std::string("epoll_wait: ") +
                                  strerror(errno));
     }
+    dispatching_ = true;
     for (int i = 0; i < n; ++i) {
         int fd = (int)(uint32_t)evs[i].data.u64;
         uint32_t gen = (uint32_t)(evs[i].data.u64 >> 32);
         auto it = fds_.find(fd);
         if (it == fds_.end()) continue;  // removed by earlier callback
         if (it->second.gen != gen) continue;  // fd reused in this batch
-        // Copy: callback may delFd itself.
-        FdCallback cb = it->second.cb;
+        /* the callback may delFd itself: retire() keeps the function
+         * alive until the round is over */
+        FdCallback& cb = *it->second.cb;
         cb(evs[i].events);
     }
+    dispatching_ = false;
+    retired_.clear();
     fireTimers();
 }
 

@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <queue>
 #include <thread>
@@ -68,6 +69,29 @@ class EventLoop {
      * the mutex outlives the loop's last iteration. */
     void setDispatchLock(std::mutex* m) { dispatchLock_ = m; }
 
+    /* For what has no fd to become ready - shared-memory rings. Called
+     * on the loop thread (under the dispatch lock, where there is one):
+     *
+     *  - hook(false) once per round, after deferred tasks and before
+     *    epoll_wait: look at the rings and do the work found there.
+     *    Returns Work if there was any, Idle if there was none, and
+     *    NoRings if the hook has no ring to look at right now: the
+     *    round then runs exactly as on a loop without a hook.
+     *  - hook(true) only when the loop is about to sleep for real, that
+     *    is after a whole round in which neither the hook nor any fd had
+     *    anything: announce that this thread is going to sleep (so that
+     *    the peers know to wake it) and look once more. Returns Work if
+     *    something has arrived meanwhile: the loop then does not sleep.
+     *
+     * While there are rings, a round that follows one with work or
+     * events only polls the fds (epoll_wait with a zero timeout), so a
+     * loop under load never announces sleep and nobody spends a syscall
+     * on waking it; going idle costs one empty round. One hook per
+     * loop; set before run(). */
+    enum class Park { NoRings, Idle, Work };
+    using ParkHook = std::function<Park(bool park)>;
+    void setBeforePark(ParkHook h) { beforePark_ = std::move(h); }
+
     /* True on the thread that is running this loop. */
     bool inLoopThread() const {
         return loopThread_.load(std::memory_order_relaxed) ==
@@ -97,19 +121,32 @@ class EventLoop {
      * with it (data.u64 = gen<<32 | fd) so a stale queued event for a
      * closed-and-reused fd within one epoll_wait batch is dropped
      * instead of being delivered to the new registration (fd-reuse ABA). */
+    /* The callback lives on the heap at a stable address and dispatch
+     * calls it by reference: nothing is copied or counted per event. A
+     * delFd (or a re-registration) made while callbacks are being
+     * dispatched - typically by the callback about itself - moves the
+     * function into retired_, which is emptied after the round, so the
+     * reference stays good for as long as the callback runs. */
     struct FdReg {
         uint32_t gen;
-        FdCallback cb;
+        std::unique_ptr<FdCallback> cb;
     };
+    void retire(FdReg& r) {
+        if (dispatching_ && r.cb) retired_.push_back(std::move(r.cb));
+    }
 
     int epfd_;
     std::atomic<bool> running_{false};
     std::map<int, FdReg> fds_;
+    std::vector<std::unique_ptr<FdCallback>> retired_;
+    bool dispatching_ = false;  /* inside the fd callback loop */
     uint32_t nextFdGen_ = 1;
     std::priority_queue<Timer, std::vector<Timer>, std::greater<Timer>> heap_;
     std::map<uint64_t, TimerCallback> timers_;  // id -> cb (absent=cancelled)
     uint64_t nextTimerId_ = 1;
     std::vector<TimerCallback> deferred_;
+    ParkHook beforePark_;
+    bool hadWork_ = false;  /* the previous round found some */
 
     int wakeFd_ = -1;
     std::mutex* dispatchLock_ = nullptr;

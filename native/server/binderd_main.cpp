@@ -14,7 +14,9 @@
  *              tree, used by tests/bench config 1)
  * Env: ZK_HOST (lib/zk.js:34), ZK_PORT (test/helper.js:54), LOG_LEVEL,
  * BINDER_SERVE_THREADS (overrides config key serveThreads; threads that
- * serve balancer connections, 1 = the main thread alone).
+ * serve balancer connections, 1 = the main thread alone),
+ * BINDER_BAL_SHM (overrides config key balancerShm; 0 = decline a
+ * balancer's offer of shared-memory rings and stay on the stream).
  * Option precedence: defaults < config file < CLI (main.js:105).
  * Metrics HTTP on port+1000 (main.js:144-152).
  */
@@ -211,6 +213,10 @@ int main(int argc, char** argv) {
         sopts.serveThreads = atoi(st);
     if (sopts.serveThreads < 1) sopts.serveThreads = 1;
     if (sopts.serveThreads > 64) sopts.serveThreads = 64;
+    if (opts.get("balancerShm").isBool())
+        sopts.balancerShm = opts.get("balancerShm").asBool();
+    if (const char* e = getenv("BINDER_BAL_SHM"); e && *e)
+        sopts.balancerShm = atoi(e) != 0;
 
     DnsServer server(&loop, log, sopts, &engine, &collector);
     server.setStore(store);

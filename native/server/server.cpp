@@ -103,6 +103,12 @@ DnsServer::DnsServer(EventLoop* loop, Logger log, ServerOptions opts,
         "total time to process Binder requests");
     sizeHist_ = collector->histogram("binder_response_size_bytes",
                                      "size in bytes of Binder responses");
+    shmDoorbellCounter_ = collector->counter(
+        "binder_balancer_shm_doorbells",
+        "doorbells rung to wake a balancer across shared-memory rings");
+    shmDrainCounter_ = collector->counter(
+        "binder_balancer_shm_drains",
+        "takes from a shared-memory query ring that returned data");
 
     const EngineConfig& cfg = engine_->config();
     if (!cfg.dnsDomain.empty()) dotDomain_ = "." + cfg.dnsDomain;
@@ -279,6 +285,9 @@ bool DnsServer::pooled() const {
 bool DnsServer::start() {
     if (!openUdp() || !openTcp()) return false;
     if (!opts_.balancerSocket.empty() && !openBalancer()) return false;
+    if (!opts_.balancerSocket.empty() && opts_.balancerShm)
+        loop_->setBeforePark(
+            [this](bool park) { return balBeforePark(main_, park); });
     if (pooled()) {
         /* from here on the main loop dispatches under the serving lock */
         loop_->setDispatchLock(&serveMu_);
@@ -288,6 +297,12 @@ bool DnsServer::start() {
             ctx->ownLoop = std::make_unique<EventLoop>();
             ctx->loop = ctx->ownLoop.get();
             EventLoop* l = ctx->loop;
+            if (opts_.balancerShm) {
+                ServeCtx* cp = ctx.get();
+                l->setBeforePark([this, cp](bool park) {
+                    return balBeforePark(*cp, park);
+                });
+            }
             ctx->thread = std::thread([l]() { l->run(); });
             pool_.push_back(std::move(ctx));
         }
@@ -608,6 +623,12 @@ void DnsServer::foldShards() {
     };
     fold(main_);
     for (auto& c : pool_) fold(*c);
+    auto foldShm = [this](ServeCtx& c) {
+        shmDoorbellCounter_->fold("", c.shmDoorbells, c.shmDoorbellsFold);
+        shmDrainCounter_->fold("", c.shmDrains, c.shmDrainsFold);
+    };
+    foldShm(main_);
+    for (auto& c : pool_) foldShm(*c);
     /* the first fast-path reply of either type brings both series */
     if (queriesServed() != servedSlow_) {
         reqCounter_->slot(kA);
@@ -1378,18 +1399,119 @@ void DnsServer::adoptBal(ServeCtx& ctx, int fd) {
     });
 }
 
+DnsServer::BalConn::~BalConn() {
+    for (int i = 0; i < nRxFds; ++i) close(rxFds[i]);
+}
+
+void DnsServer::dropRxFds(BalConn* c) {
+    for (int i = 0; i < c->nRxFds; ++i) close(c->rxFds[i]);
+    c->nRxFds = 0;
+}
+
 void DnsServer::closeBal(ServeCtx& ctx, BalConn* c) {
     if (c->closed) return;
     c->closed = true;
     ctx.loop->delFd(c->fd);
     close(c->fd);
+    if (c->shmOn) {
+        ctx.loop->delFd(c->shm.wakeMe);
+        auto& v = ctx.shmConns;
+        v.erase(std::remove(v.begin(), v.end(), c), v.end());
+        c->shmOn = c->rxShm = c->txShm = false;
+    }
+    c->shm.close();
+    dropRxFds(c);
     ctx.balConns.erase(c->fd);
 }
 
-void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
+/* SHM_OFFER, at its place in the batch. Accepting means: map the region
+ * the balancer made, check that it is what the offer says, register our
+ * doorbell, and queue SHM_OK as the last reply bytes of the stream.
+ * Declining is silent: the descriptors are closed and the balancer,
+ * never hearing SHM_OK, stays on the stream. */
+void DnsServer::acceptShm(ServeCtx& ctx, BalConn* c, const uint8_t* p,
+                          size_t len) {
+    bool ok = opts_.balancerShm && !c->shmOn &&
+              c->nRxFds == bsock::kShmOfferFds &&
+              len >= bsock::kShmOfferLen &&
+              bsock::getU32(p) == shm::kVersion &&
+              bsock::getU32(p + 8) == shm::kDataOff &&
+              c->shm.region.attach(c->rxFds[0], bsock::getU32(p + 4)) &&
+              setNonBlocking(c->rxFds[1]) && setNonBlocking(c->rxFds[2]);
+    if (ok) {
+        BalConn* raw = c;
+        ServeCtx* cp = &ctx;
+        try {
+            ctx.loop->addFd(c->rxFds[1], EPOLLIN | EPOLLET,
+                            [this, cp, raw](uint32_t) {
+                                onBalBell(*cp, raw);
+                            });
+        } catch (const std::runtime_error&) {
+            ok = false;  /* not something epoll can wait on */
+        }
+    }
+    if (!ok) {
+        log_.debug("shared-memory offer declined");
+        c->shm.region.reset();
+        dropRxFds(c);
+        return;
+    }
+    close(c->rxFds[0]);  /* mapped */
+    c->shm.wakeMe = c->rxFds[1];
+    c->shm.wakePeer = c->rxFds[2];
+    c->nRxFds = 0;
+    c->shm.attachEnds(false);
+    c->shmOn = true;
+    ctx.shmConns.push_back(c);
+    bsock::appendFrame(c->out, bsock::FRAME_SHM_OK, "");
+    c->streamEnd = c->out.size();
+}
+
+/* Reply bytes into the ring: what fits now; the rest stays in `out`
+ * and the balancer rings our doorbell when it has made room. */
+void DnsServer::flushToRing(ServeCtx& ctx, BalConn* c) {
+    bool wrote = false;
+    c->writeBlocked = false;
     while (c->outOff < c->out.size()) {
+        size_t n = c->shm.tx.write(c->out.data() + c->outOff,
+                                   c->out.size() - c->outOff);
+        c->outOff += n;
+        if (n != 0) wrote = true;
+        if (c->outOff >= c->out.size()) break;
+        if (c->shm.tx.bad()) {
+            closeBal(ctx, c);
+            return;
+        }
+        if (c->shm.tx.waitForSpace()) {
+            c->writeBlocked = true;
+            break;
+        }
+    }
+    if (wrote && c->shm.tx.consumerNeedsWake()) {
+        shm::ringDoorbell(c->shm.wakePeer);
+        ctx.shmDoorbells.bump();
+    }
+    if (c->outOff >= c->out.size()) {
+        c->out.clear();
+        c->outOff = 0;
+    } else if (c->outOff > (1u << 20)) {
+        c->out.erase(0, c->outOff);
+        c->outOff = 0;
+    }
+}
+
+void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
+    if (c->closed) return;
+    if (c->txShm) {
+        flushToRing(ctx, c);
+        return;
+    }
+    /* with a SHM_OK queued, the stream gets the bytes up to its end */
+    while (true) {
+        size_t end = c->streamEnd != 0 ? c->streamEnd : c->out.size();
+        if (c->outOff >= end) break;
         ssize_t nw = write(c->fd, c->out.data() + c->outOff,
-                           c->out.size() - c->outOff);
+                           end - c->outOff);
         if (nw > 0) {
             c->outOff += (size_t)nw;
             continue;
@@ -1400,6 +1522,7 @@ void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
              * against the memmove-per-write of erase(0, nw)) */
             if (c->outOff > (1u << 20)) {
                 c->out.erase(0, c->outOff);
+                if (c->streamEnd != 0) c->streamEnd -= c->outOff;
                 c->outOff = 0;
             }
             if (!c->writeBlocked) {
@@ -1411,18 +1534,59 @@ void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
         closeBal(ctx, c);
         return;
     }
-    c->out.clear();
-    c->outOff = 0;
     if (c->writeBlocked) {
         c->writeBlocked = false;
         ctx.loop->modFd(c->fd, EPOLLIN);
     }
+    if (c->streamEnd != 0) {
+        /* SHM_OK is on the wire: the ring from here on */
+        c->streamEnd = 0;
+        c->txShm = true;
+        flushToRing(ctx, c);
+        return;
+    }
+    c->out.clear();
+    c->outOff = 0;
 }
 
-/* Runs on ctx's thread. For a pool thread that means without the
- * serving lock: table hits, PINGs and the socket I/O touch nothing but
- * ctx and c. Everything else takes the lock (ServeLock) for the one
- * frame it is about, at that frame's place in the batch. */
+/* the balancer's doorbell: queries in the ring, or room in the reply
+ * ring we were waiting for (edge-triggered; the eventfd is not read) */
+void DnsServer::onBalBell(ServeCtx& ctx, BalConn* c) {
+    std::shared_ptr<BalConn> keep = c->shared_from_this();
+    if (c->closed) return;
+    if (c->txShm && c->writeBlocked) balFlush(ctx, c);
+    if (!c->closed && c->rxShm) serveBal(ctx, c, true);
+}
+
+/* The hook of ctx's loop (loop.hpp). Every round: serve what the query
+ * rings hold - under load there is something, and nobody had to wake us
+ * for it. Before a real sleep: tell the balancers, and look once more. */
+EventLoop::Park DnsServer::balBeforePark(ServeCtx& ctx, bool park) {
+    auto& v = ctx.shmConns;
+    EventLoop::Park out = EventLoop::Park::NoRings;
+    if (park) {
+        for (BalConn* c : v) {
+            if (!c->rxShm) continue;
+            if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
+            if (!c->shm.rx.park()) out = EventLoop::Park::Work;
+        }
+        return out;
+    }
+    for (size_t i = 0; i < v.size();) {
+        BalConn* c = v[i];
+        if (c->rxShm) {
+            if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
+            if (c->shm.rx.readable() != 0 || c->shm.rx.bad()) {
+                std::shared_ptr<BalConn> keep = c->shared_from_this();
+                serveBal(ctx, c, true);
+                out = EventLoop::Park::Work;
+            }
+        }
+        if (i < v.size() && v[i] == c) ++i;  /* else it was closed */
+    }
+    return out;
+}
+
 void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
     std::shared_ptr<BalConn> keep = ctx.balConns[c->fd];
     if (events & (EPOLLHUP | EPOLLERR)) {
@@ -1431,7 +1595,22 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
     }
     if (events & EPOLLOUT) balFlush(ctx, c);
     if (c->closed || !(events & EPOLLIN)) return;
+    if (c->rxShm) {
+        /* SHM_GO was the balancer's last word on the stream: all that
+         * can show up here now is its end, or a peer gone wrong */
+        char junk[64];
+        ssize_t nr = read(c->fd, junk, sizeof(junk));
+        if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return;
+        closeBal(ctx, c);
+        return;
+    }
+    serveBal(ctx, c, false);
+}
 
+/* Take a batch of bytes off the socket, or off the query ring once the
+ * connection has moved there, and serve the frames in it. The caller
+ * holds a reference to c. */
+void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
     /* Bounded batch per epoll event: the GSO-era balancer can queue
      * megabytes behind one connection, and draining it all here would
      * process tens of thousands of queries (10+ ms) while the other
@@ -1446,9 +1625,60 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
      * event. */
     constexpr size_t kMaxReadPerEvent = 128 * 1024;
     size_t got = 0;
-    while (got < kMaxReadPerEvent) {
+    if (fromRing) {
+        /* the same quota, copied to the same place; a ring drained
+         * short of it is empty, and whatever is left is found by the
+         * poll before this thread sleeps */
+        got = c->shm.rx.read(c->in.tail(kMaxReadPerEvent),
+                             kMaxReadPerEvent);
+        if (c->shm.rx.bad()) {
+            closeBal(ctx, c);
+            return;
+        }
+        if (got == 0) return;
+        c->in.commit(got);
+        ctx.shmDrains.bump();
+        if (c->shm.rx.producerNeedsWake()) {
+            shm::ringDoorbell(c->shm.wakePeer);
+            ctx.shmDoorbells.bump();
+        }
+    }
+    while (!fromRing && got < kMaxReadPerEvent) {
         size_t want = kMaxReadPerEvent - got;
-        ssize_t nr = read(c->fd, c->in.tail(want), want);
+        /* recvmsg, not read: a SHM_OFFER brings descriptors, and they
+         * arrive with the read that returns its first byte */
+        struct iovec iov = {c->in.tail(want), want};
+        alignas(struct cmsghdr) char
+            cbuf[CMSG_SPACE(sizeof(int) * bsock::kShmOfferFds)];
+        struct msghdr mh {};
+        mh.msg_iov = &iov;
+        mh.msg_iovlen = 1;
+        mh.msg_control = cbuf;
+        mh.msg_controllen = sizeof(cbuf);
+        const bool mayOffer = opts_.balancerShm && !c->shmOn;
+        ssize_t nr = mayOffer ? recvmsg(c->fd, &mh, MSG_CMSG_CLOEXEC)
+                              : read(c->fd, iov.iov_base, want);
+        if (mayOffer && nr >= 0 && mh.msg_controllen != 0) {
+            for (struct cmsghdr* cm = CMSG_FIRSTHDR(&mh); cm != nullptr;
+                 cm = CMSG_NXTHDR(&mh, cm)) {
+                if (cm->cmsg_level != SOL_SOCKET ||
+                    cm->cmsg_type != SCM_RIGHTS)
+                    continue;
+                /* only the latest set is kept (what did not fit in
+                 * cbuf the kernel has closed already) */
+                dropRxFds(c);
+                size_t n = (cm->cmsg_len - CMSG_LEN(0)) / sizeof(int);
+                for (size_t i = 0; i < n; ++i) {
+                    int fd;
+                    memcpy(&fd, CMSG_DATA(cm) + i * sizeof(int),
+                           sizeof(int));
+                    if (c->nRxFds < bsock::kShmOfferFds)
+                        c->rxFds[c->nRxFds++] = fd;
+                    else
+                        close(fd);
+                }
+            }
+        }
         if (nr > 0) {
             c->in.commit((size_t)nr);
             got += (size_t)nr;
@@ -1480,9 +1710,11 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
      * order. With the table bypassed (info/debug logging) nothing is
      * parsed ahead.
      */
-    enum : uint8_t { kSkip, kPing, kQuery, kFastQuery };
+    enum : uint8_t { kSkip, kPing, kQuery, kFastQuery, kShmOffer, kShmGo };
     struct PipeFrame {
         uint8_t kind;
+        const uint8_t* raw;  /* kShmOffer: payload, in c->in */
+        uint32_t rawLen;
         bsock::QueryFrame qf;
         FastQuery q;
         uint32_t off;   /* probe() result, good while gen matches */
@@ -1494,6 +1726,7 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
     const bool memo = answersOn() && engineStore_ != nullptr;
     bsock::FrameStatus st = bsock::FrameStatus::Ok;
     size_t fetched = 0, probed = 0, served = 0;
+    bool sawGo = false;
     while (true) {
         /* stage 1: take frames off the buffer, up to the lookahead */
         while (st == bsock::FrameStatus::Ok &&
@@ -1513,6 +1746,12 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
                     p.q.hash = answerHash(p.q);
                     answers.prefetchSlot(p.q.hash);
                 }
+            } else if (fr.type == bsock::FRAME_SHM_OFFER) {
+                p.kind = kShmOffer;
+                p.raw = fr.payload;
+                p.rawLen = fr.plen;
+            } else if (fr.type == bsock::FRAME_SHM_GO) {
+                p.kind = kShmGo;
             } else {
                 p.kind = kSkip;
             }
@@ -1535,6 +1774,16 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
             continue;
         }
         if (p.kind == kSkip) continue;
+        if (p.kind == kShmOffer) {
+            acceptShm(ctx, c, p.raw, p.rawLen);
+            continue;
+        }
+        if (p.kind == kShmGo) {
+            /* the balancer's queries continue in the ring (looked at
+             * before this thread sleeps, at the latest) */
+            if (c->shmOn && !c->rxShm) c->rxShm = sawGo = true;
+            continue;
+        }
         const bsock::QueryFrame& qf = p.qf;
         ReplySink sink(&c->out, qf.reqId);
         const bool udp = qf.proto == 0;
@@ -1573,7 +1822,9 @@ void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
             process(ctx, qf.dns, qf.dnsLen, udp, ci, sink, target);
         }
     }
-    if (st == bsock::FrameStatus::Bad) {
+    /* SHM_GO ends the stream: a partial frame behind it can never be
+     * completed */
+    if (st == bsock::FrameStatus::Bad || (sawGo && c->in.size() != 0)) {
         closeBal(ctx, c);
         return;
     }

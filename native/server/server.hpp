@@ -33,6 +33,7 @@
 
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
+#include "../common/shmpipe.hpp"
 #include "../engine/engine.hpp"
 #include "answertab.hpp"
 #include "framebuf.hpp"
@@ -48,6 +49,9 @@ struct ServerOptions {
     /* threads serving balancer connections; 1 = none besides the main
      * thread. See defaultServeThreads(). */
     int serveThreads = 1;
+    /* accept a balancer's offer of shared-memory rings for its
+     * connection (config balancerShm, environment BINDER_BAL_SHM) */
+    bool balancerShm = true;
 };
 
 /* clamp(cpus / 4, 1, 4), cpus being what this process may actually use:
@@ -166,6 +170,23 @@ class DnsServer {
         size_t outOff = 0;  /* flushed prefix of `out` (write cursor) */
         bool writeBlocked = false;
         bool closed = false;
+
+        /* Shared-memory rings (protocol.hpp, types 5-7). rxFds: the
+         * descriptors that arrived with the stream bytes, until the
+         * SHM_OFFER frame they belong to is parsed. shmOn: the offer
+         * was accepted (region mapped, doorbell registered). streamEnd:
+         * end of the SHM_OK frame in `out`; bytes before it still go to
+         * the socket, and once they have, txShm is set and everything
+         * after goes to the reply ring. rxShm: SHM_GO seen, queries are
+         * taken from the query ring. */
+        shm::Link shm;
+        int rxFds[bsock::kShmOfferFds] = {-1, -1, -1};
+        int nRxFds = 0;
+        bool shmOn = false;
+        bool rxShm = false;
+        bool txShm = false;
+        size_t streamEnd = 0;
+        ~BalConn();
     };
 
     /* Where an asynchronous (recursion) reply goes. Non-owning and
@@ -193,6 +214,12 @@ class DnsServer {
     void onBalAccept();
     void adoptBal(ServeCtx& ctx, int fd);
     void onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events);
+    void onBalBell(ServeCtx& ctx, BalConn* c);
+    void serveBal(ServeCtx& ctx, BalConn* c, bool fromRing);
+    void acceptShm(ServeCtx& ctx, BalConn* c, const uint8_t* p, size_t len);
+    void dropRxFds(BalConn* c);
+    void flushToRing(ServeCtx& ctx, BalConn* c);
+    EventLoop::Park balBeforePark(ServeCtx& ctx, bool park);
 
     /*
      * Decode + resolve + encode. Returns true when the answer is
@@ -282,6 +309,11 @@ class DnsServer {
         HitShards hits;
         EventLoop* loop = nullptr;
         std::map<int, std::shared_ptr<BalConn>> balConns;
+        /* those of balConns that have rings, polled before the thread
+         * sleeps; and what the thread did with them (owner writes) */
+        std::vector<BalConn*> shmConns;
+        CounterShard shmDoorbells, shmDrains;
+        CounterFold shmDoorbellsFold, shmDrainsFold;
         bool pooled = false;
 
         std::atomic<uint64_t> inboxSeq{0};
@@ -373,6 +405,8 @@ class DnsServer {
     RecursionIface* recursion_ = nullptr;
 
     Counter* reqCounter_ = nullptr;
+    Counter* shmDoorbellCounter_ = nullptr;
+    Counter* shmDrainCounter_ = nullptr;
     Histogram* latHist_ = nullptr;
     Histogram* sizeHist_ = nullptr;
 

@@ -9,10 +9,13 @@ usage: cpu_apportion.py [--procs 8] [--workers 8] [--threads 6]
                         [--window 256] [--ramp 2] [--tag NAME]
 
 Every component is reported as total cores and split into user and
-system time. For the balancer the cost per query (core-us, user and
-system) and the shape of its hot path over the window are added from
-its stats socket: mean reply-run length, share of replies that left
-singly, replies per backend read, queries per received UDP message.
+system time. For the balancer and for binderd the cost per query
+(core-us, user and system) is added, and from the balancer's stats
+socket the shape of its hot path over the window: mean reply-run
+length, share of replies that left singly, replies per backend read,
+queries per received UDP message, and - with the backend hop on
+shared-memory rings - doorbells rung, ring drains, doorbells per drain
+and the transports in use.
 BALANCER_BIN selects the balancer binary (binder_amd/harness.py), so a
 parent build and a new one can alternate inside one box visit.
 
@@ -121,19 +124,26 @@ def main():
             total += user + syst
         out["total_cores"] = round(total, 2)
         if out["qps"] > 0:
-            user, syst = split["balancer"]
             per_q = 1e6 / out["qps"]  # cores -> core-us per query
-            out["balancer_core_us_per_query"] = round(
-                (user + syst) * per_q, 4)
-            out["balancer_user_us_per_query"] = round(user * per_q, 4)
-            out["balancer_sys_us_per_query"] = round(syst * per_q, 4)
+            for k in ("balancer", "binderd"):
+                user, syst = split[k]
+                out[k + "_core_us_per_query"] = round(
+                    (user + syst) * per_q, 4)
+                out[k + "_user_us_per_query"] = round(user * per_q, 4)
+                out[k + "_sys_us_per_query"] = round(syst * per_q, 4)
         # hot-path shape over the window (absent from older balancers)
         d = {k: st1[k] - st0[k] for k in
              ("udp_queries", "udp_replies", "reply_runs",
               "reply_run_segments", "reply_singles", "backend_reads",
-              "udp_rx_msgs") if k in st1 and k in st0}
+              "udp_rx_msgs", "shm_doorbells", "shm_drains")
+             if k in st1 and k in st0}
         if "reply_runs" in d:
             out.update(d)
+            if d.get("shm_drains"):
+                out["doorbells_per_drain"] = round(
+                    d["shm_doorbells"] / d["shm_drains"], 4)
+            out["transports"] = sorted(
+                {b.get("transport", "stream") for b in st1["backends"]})
             if d["reply_runs"]:
                 out["mean_run_len"] = round(
                     d["reply_run_segments"] / d["reply_runs"], 2)
