@@ -186,6 +186,45 @@ check-serve-threads: all $(BUILD)/tsan/binderd
 	    tests/test_serve_threads.py tests/test_answer_table.py \
 	    tests/test_bsock_ingress.py
 
+# Sanitizer run of the DNS codec (dns/codec.cpp) in a stand-alone
+# program: a seeded corpus of encoded messages of every record type,
+# their prefixes, mutations and random buffers, each decoded from a heap
+# block of exactly its length; what decodes is re-encoded and must decode
+# to the same message. Host-only, CPU-only.
+$(BUILD)/codec_check: native/dns/codec_check_main.cpp native/dns/codec.cpp \
+		native/dns/codec.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    native/dns/codec_check_main.cpp native/dns/codec.cpp -o $@
+
+check-codec: $(BUILD)/codec_check
+	$(BUILD)/codec_check 1 20
+
+# AddressSanitizer+UBSan run of the served wire: binderd itself (a daemon
+# with its own main) built with -fsanitize=address,undefined into
+# $(BUILD)/asan, and the suites that put hand-built and hostile queries
+# on its sockets run against it. The balancer and the Python side are
+# the ordinary builds. tests/test_dns_wire_served.py fails on a sanitizer
+# report in a daemon's log or a daemon that exited on its own. Host-only,
+# CPU-only.
+ASAN_FLAGS := -O1 -g -std=c++20 -fsanitize=address,undefined \
+	-fno-sanitize-recover=all -fno-omit-frame-pointer \
+	-Wall -Wextra -Werror -Wno-unused-parameter
+ASAN_OBJS := $(TSAN_SRCS:%.cpp=$(BUILD)/asan/obj/%.o)
+
+$(BUILD)/asan/obj/%.o: %.cpp
+	@mkdir -p $(dir $@)
+	$(CXX) $(ASAN_FLAGS) -MMD -MP -c $< -o $@
+
+$(BUILD)/asan/binderd: $(ASAN_OBJS)
+	$(CXX) $(ASAN_FLAGS) $^ -o $@ -lssl -lcrypto -lpthread
+
+check-wire-asan: all $(BUILD)/asan/binderd
+	BINDERD_BIN=$(CURDIR)/$(BUILD)/asan/binderd $(PYTHON) -m pytest -q \
+	    tests/test_dns_wire_served.py tests/test_hostile_inputs.py \
+	    tests/test_fastpath.py
+
 # release tarball layout under /opt/binder-amd (the reference ships
 # /opt/smartdc/binder with balancer+smf_adjust in lib/ and zklog in
 # bin/; Makefile:178-229 there)
@@ -212,4 +251,5 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
-	check-replyruns check-shmpipe check-serve-threads release
+	check-replyruns check-shmpipe check-serve-threads check-codec \
+	check-wire-asan release

@@ -162,7 +162,9 @@ namespace {
 
 struct Encoder {
     std::vector<uint8_t>& buf;
-    bool ok = true;  // false: a name had a >63-byte label (unencodable)
+    // false: a name cannot be written (a label over 63 octets or empty,
+    // or more than 255 octets in all)
+    bool ok = true;
     explicit Encoder(std::vector<uint8_t>& b) : buf(b) { buf.clear(); }
     // Compression table: (suffix view, wire offset). Views reference
     // the record name strings, which outlive the encode; linear scan
@@ -201,6 +203,17 @@ struct Encoder {
      * trailing dot. NOTE: the view must stay valid for the whole
      * encode (record name strings do). */
     void encodeName(std::string_view rest, bool compress = true) {
+        /* RFC 1035 2.3.4: 255 octets on the wire, length octets and
+         * the root included. n labels of presentation size s (n - 1
+         * dots among them) take s + 2; a trailing dot stands for the
+         * root and adds nothing. */
+        size_t pres = rest.size();
+        if (pres > 0 && rest.back() == '.') --pres;
+        if (pres > 253) {
+            ok = false;
+            u8(0);
+            return;
+        }
         while (!rest.empty()) {
             if (compress) {
                 const uint16_t* off = findOffset(rest);
@@ -218,10 +231,11 @@ struct Encoder {
             rest = dot == std::string_view::npos
                        ? std::string_view()
                        : rest.substr(dot + 1);
-            if (label.size() > 63) {
+            if (label.size() > 63 || label.empty()) {
                 /* DNS labels cap at 63 bytes; an over-long label from
                  * store/config data must fail the encode rather than be
-                 * silently altered on the wire. */
+                 * silently altered on the wire. An empty one ("a..b",
+                 * ".a") would be written as a root octet mid-name. */
                 ok = false;
                 u8(0);
                 return;
@@ -344,10 +358,12 @@ bool encodeImpl(const Message& m, bool truncated,
 
 void Message::encodeInto(std::vector<uint8_t>& out, size_t maxSize) const {
     if (!encodeImpl(*this, false, out)) {
-        /* A record carried a >63-byte label: answer SERVFAIL instead of
-         * emitting a silently altered name. Client-decoded questions
-         * can never hit this (wire labels cap at 63), but re-check and
-         * drop them too if a synthesized question is itself bad. */
+        /* A record carried a name that cannot be written (a label over
+         * 63 octets, or over 255 octets in all): answer SERVFAIL instead
+         * of emitting a silently altered name. Client-decoded questions
+         * can never hit this (decode applies the same limits), but
+         * re-check and drop them too if a synthesized question is itself
+         * bad. */
         Message fail;
         fail.header = header;
         fail.header.qr = true;
@@ -398,19 +414,33 @@ struct Decoder {
         return true;
     }
 
-    /* Decode a possibly-compressed name starting at pos. */
-    bool name(std::string& out) { return nameAt(pos, out, 0, &pos); }
+    /* A pointer must point backwards, so a run of pointers ends by
+     * itself, and every label counts toward the 255 octets of a name:
+     * that bounds the walk. The cap on jumps only keeps a crafted run
+     * of pointers to pointers cheap; a name has at most 127 labels and
+     * no sensible writer spends more than one pointer on each. */
+    static constexpr int kMaxJumps = 128;
 
-    bool nameAt(size_t at, std::string& out, int depth, size_t* endPos) {
-        if (depth > 16) return false;
+    /* Decode a possibly-compressed name starting at pos. The octets in
+     * place (up to the first pointer, or the root) must end by `limit`:
+     * the end of the message, or of the rdata the name is part of. */
+    bool name(std::string& out) { return nameAt(pos, out, len, &pos); }
+    bool name(std::string& out, size_t limit) {
+        return nameAt(pos, out, limit, &pos);
+    }
+
+    bool nameAt(size_t at, std::string& out, size_t limit, size_t* endPos) {
+        int depth = 0;
         size_t p = at;
         bool jumped = false;
         size_t afterFirstJump = 0;
+        size_t wire = 1;  /* the root octet (RFC 1035 2.3.4) */
         while (true) {
-            if (p >= len) return false;
+            const size_t end = jumped ? len : limit;
+            if (p >= end) return false;
             uint8_t l = data[p];
             if ((l & 0xC0) == 0xC0) {
-                if (p + 1 >= len) return false;
+                if (p + 1 >= end) return false;
                 size_t target = ((size_t)(l & 0x3F) << 8) | data[p + 1];
                 if (!jumped) {
                     afterFirstJump = p + 2;
@@ -418,18 +448,23 @@ struct Decoder {
                 }
                 if (target >= p) return false;  // forward pointers invalid
                 p = target;
-                ++depth;
-                if (depth > 16) return false;
+                if (++depth > kMaxJumps) return false;
                 continue;
             }
             if ((l & 0xC0) != 0) return false;  // reserved label types
             ++p;
             if (l == 0) break;
-            if (p + l > len) return false;
+            if (p + l > end) return false;
+            wire += 1 + (size_t)l;
+            if (wire > 255) return false;
+            /* A '.' inside a label has no place in the dotted string
+             * the engine and the encoder work on: "a.b" as one label
+             * would come back out as two. Refused like any wire this
+             * server cannot represent (docs/PARITY.md). */
+            if (memchr(data + p, '.', l) != nullptr) return false;
             if (!out.empty()) out.push_back('.');
             out.append((const char*)data + p, l);
             p += l;
-            if (out.size() > 255) return false;
         }
         *endPos = jumped ? afterFirstJump : p;
         return true;
@@ -456,10 +491,11 @@ struct Decoder {
         case TYPE_NS:
         case TYPE_CNAME:
         case TYPE_PTR:
-            if (!name(r.target)) return false;
-            pos = rdEnd;
+            if (!name(r.target, rdEnd)) return false;
             break;
         case TYPE_TXT: {
+            /* RFC 1035 3.3.14: one or more character-strings */
+            if (rdlen == 0) return false;
             while (pos < rdEnd) {
                 uint8_t n;
                 if (!u8(n)) return false;
@@ -467,29 +503,29 @@ struct Decoder {
                 r.target.append((const char*)data + pos, n);
                 pos += n;
             }
-            pos = rdEnd;
             break;
         }
         case TYPE_SRV:
+            if (rdlen < 6) return false;
             if (!u16(r.priority) || !u16(r.weight) || !u16(r.port))
                 return false;
-            if (!name(r.target)) return false;
-            pos = rdEnd;
+            if (!name(r.target, rdEnd)) return false;
             break;
         case TYPE_SOA:
-            if (!name(r.soa.mname) || !name(r.soa.rname)) return false;
+            if (!name(r.soa.mname, rdEnd) || !name(r.soa.rname, rdEnd))
+                return false;
             if (!u32(r.soa.serial) || !u32(r.soa.refresh) ||
                 !u32(r.soa.retry) || !u32(r.soa.expire) ||
                 !u32(r.soa.minimum))
                 return false;
-            pos = rdEnd;
             break;
         default:
             r.rdataRaw.assign(data + pos, data + rdEnd);
             pos = rdEnd;
             break;
         }
-        return true;
+        /* typed rdata must end where rdlength says (RFC 1035 3.2.1) */
+        return pos == rdEnd;
     }
 };
 

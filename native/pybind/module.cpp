@@ -50,19 +50,39 @@ static py::dict recordToDict(const dns::Record& r) {
         d["mname"] = pystr(r.soa.mname);
         d["rname"] = pystr(r.soa.rname);
         d["serial"] = r.soa.serial;
+        d["refresh"] = r.soa.refresh;
+        d["retry"] = r.soa.retry;
+        d["expire"] = r.soa.expire;
         d["minimum"] = r.soa.minimum;
         break;
     case dns::TYPE_OPT:
         d["udp_size"] = r.rclass;
+        d["rdata"] = r.rdataRaw;  /* a list of ints: stays JSON-able */
+        break;
+    case dns::TYPE_NS:
+    case dns::TYPE_CNAME:
+    case dns::TYPE_PTR:
+    case dns::TYPE_TXT:
+        d["target"] = pystr(r.target);
         break;
     default:
-        d["target"] = pystr(r.target);
+        d["rdata"] = r.rdataRaw;  /* a list of ints: stays JSON-able */
         break;
     }
     return d;
 }
 
+static dns::Record recordFromDictTyped(const py::dict& d);
+
+/* The typed constructors fix the class at IN; "class" overrides it. */
 static dns::Record recordFromDict(const py::dict& d) {
+    dns::Record r = recordFromDictTyped(d);
+    if (d.contains("class") && r.type != dns::TYPE_OPT)
+        r.rclass = d["class"].cast<uint16_t>();
+    return r;
+}
+
+static dns::Record recordFromDictTyped(const py::dict& d) {
     std::string type = d["type"].cast<std::string>();
     std::string name = d.contains("name") ? d["name"].cast<std::string>() : "";
     uint32_t ttl = d.contains("ttl") ? d["ttl"].cast<uint32_t>() : 0;
@@ -84,14 +104,30 @@ static dns::Record recordFromDict(const py::dict& d) {
         return dns::Record::CNAME(name, d["target"].cast<std::string>(), ttl);
     if (type == "TXT")
         return dns::Record::TXT(name, d["target"].cast<std::string>(), ttl);
-    if (type == "OPT")
-        return dns::Record::OPT(d.contains("udp_size")
-                                    ? d["udp_size"].cast<uint16_t>()
-                                    : 1400);
+    if (type == "NS") {
+        auto r = dns::Record::CNAME(name, d["target"].cast<std::string>(),
+                                    ttl);
+        r.type = dns::TYPE_NS;
+        return r;
+    }
+    if (type == "OPT") {
+        auto r = dns::Record::OPT(d.contains("udp_size")
+                                      ? d["udp_size"].cast<uint16_t>()
+                                      : 1400);
+        r.ttl = ttl;  /* extended rcode, version, DO */
+        if (d.contains("rdata"))
+            r.rdataRaw = d["rdata"].cast<std::vector<uint8_t>>();
+        return r;
+    }
     if (type == "SOA") {
         dns::SoaData soa;
         if (d.contains("mname")) soa.mname = d["mname"].cast<std::string>();
         if (d.contains("rname")) soa.rname = d["rname"].cast<std::string>();
+        if (d.contains("serial")) soa.serial = d["serial"].cast<uint32_t>();
+        if (d.contains("refresh"))
+            soa.refresh = d["refresh"].cast<uint32_t>();
+        if (d.contains("retry")) soa.retry = d["retry"].cast<uint32_t>();
+        if (d.contains("expire")) soa.expire = d["expire"].cast<uint32_t>();
         if (d.contains("minimum"))
             soa.minimum = d["minimum"].cast<uint32_t>();
         return dns::Record::SOA(name, soa, ttl);
@@ -133,6 +169,8 @@ static dns::Message messageFromDict(const py::dict& d) {
     dns::Message m;
     if (d.contains("id")) m.header.id = d["id"].cast<uint16_t>();
     if (d.contains("qr")) m.header.qr = d["qr"].cast<bool>();
+    if (d.contains("opcode"))
+        m.header.opcode = (uint8_t)(d["opcode"].cast<unsigned>() & 0xF);
     if (d.contains("aa")) m.header.aa = d["aa"].cast<bool>();
     if (d.contains("tc")) m.header.tc = d["tc"].cast<bool>();
     if (d.contains("rd")) m.header.rd = d["rd"].cast<bool>();
@@ -151,6 +189,8 @@ static dns::Message messageFromDict(const py::dict& d) {
                                 ? qd["type"].cast<std::string>()
                                 : "A";
             q.qtype = dns::typeFromName(t);
+            if (qd.contains("class"))
+                q.qclass = qd["class"].cast<uint16_t>();
             m.questions.push_back(std::move(q));
         }
     }

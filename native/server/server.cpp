@@ -312,12 +312,11 @@ bool DnsServer::start() {
     /* idle TCP sweep: DNS-over-TCP clients that neither query nor
      * close get reaped after 60s (resource protection; the balancer
      * socket is exempt — it is a long-lived peer) */
-    auto sweep = std::make_shared<std::function<void()>>();
-    *sweep = [this, sweep]() {
+    sweepTimer_ = [this]() {
         sweepIdleTcp();
-        loop_->addTimer(10000, *sweep);
+        loop_->addTimer(10000, sweepTimer_);
     };
-    loop_->addTimer(10000, *sweep);
+    loop_->addTimer(10000, sweepTimer_);
     return true;
 }
 

@@ -393,6 +393,9 @@ class DnsServer {
 
     void tcpFlush(TcpConn* c);
     void sweepIdleTcp();
+    /* the sweep's timer callback, which re-arms itself; owned here (a
+     * shared_ptr captured by its own closure would never be freed) */
+    std::function<void()> sweepTimer_;
     void balFlush(ServeCtx& ctx, BalConn* c);
     void closeTcp(TcpConn* c);
     void closeBal(ServeCtx& ctx, BalConn* c);

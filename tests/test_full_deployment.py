@@ -110,7 +110,14 @@ def test_full_stack(tmp_path):
                 timeout=2)
         assert r.status == "NOERROR"
         assert r.answers[0]["port"] == 8080
-        r = dig("worker.coal.foo.com", port=bport, timeout=2)
+        # created a moment ago: whichever backend answers may not have
+        # mirrored it yet
+        deadline = time.time() + 15
+        while time.time() < deadline:
+            r = dig("worker.coal.foo.com", port=bport, timeout=2)
+            if r.answers:
+                break
+            time.sleep(0.2)
         assert r.answers[0]["address"] == "10.88.0.2"
 
         # crash a backend: supervisor restarts it; service continues

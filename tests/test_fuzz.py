@@ -72,11 +72,26 @@ def test_engine_fuzzed_queries_via_wire():
 def test_extreme_names():
     # label/name length bounds
     long_label = "a" * 63
-    name = ".".join([long_label] * 4)  # 255 chars
+    # the legal maximum (RFC 1035 2.3.4): 255 octets on the wire, each
+    # label one more than its size, plus the root: 64 + 64 + 64 + 62 + 1
+    name = ".".join([long_label] * 3 + ["a" * 61])
     wire = n.encode_message(
         {"id": 1, "questions": [{"name": name, "type": "A"}]})
+    assert len(wire) == 12 + 255 + 4
     m = n.decode_message(wire)
     assert m["questions"][0]["name"] == name
+
+    # four 63-byte labels are 255 characters but 257 octets: not decoded
+    # (hand-packed), and not emitted (SERVFAIL, the question left out)
+    hdr = struct.pack(">HHHHHH", 1, 0, 1, 0, 0, 0)
+    too_long = hdr + (b"\x3f" + b"a" * 63) * 4 + b"\0" + \
+        struct.pack(">HH", 1, 1)
+    assert n.decode_message(too_long) is None
+    wire = n.encode_message(
+        {"id": 1, "questions": [{"name": ".".join([long_label] * 4),
+                                 "type": "A"}]})
+    m = n.decode_message(wire)
+    assert m["rcode"] == "SERVFAIL" and m["questions"] == []
 
     # oversized label gets clamped on encode, not crash
     n.encode_message(
