@@ -164,6 +164,22 @@ check-shmpipe: $(BUILD)/shmpipe_check_asan $(BUILD)/shmpipe_check_tsan
 	$(BUILD)/shmpipe_check_asan 1 100000
 	$(BUILD)/shmpipe_check_tsan 1 100000
 
+# Sanitizer run of the bsock1 transport endpoint (bsocklink.hpp) in a
+# stand-alone program: two endpoints over a socketpair and 4 KiB rings,
+# recording sinks; byte order across the stream-to-ring switch in both
+# directions, stream and ring back-pressure, corrupted ring indices, the
+# stream after the switch, an offer never answered. Host-only, CPU-only.
+$(BUILD)/bsocklink_check: native/common/bsocklink_check_main.cpp \
+		native/common/bsocklink.hpp native/common/shmpipe.hpp \
+		native/server/framebuf.hpp native/balancer/protocol.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-bsocklink: $(BUILD)/bsocklink_check
+	$(BUILD)/bsocklink_check 1
+
 # ThreadSanitizer run of the serving-thread pool: binderd itself (a daemon
 # with its own main) built with -fsanitize=thread into $(BUILD)/tsan, and
 # the pool's tests plus the two suites that pin reply order and ingress
@@ -251,5 +267,5 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
-	check-replyruns check-shmpipe check-serve-threads check-codec \
-	check-wire-asan release
+	check-replyruns check-shmpipe check-bsocklink check-serve-threads \
+	check-codec check-wire-asan release

@@ -52,8 +52,7 @@
 #include "../common/json.hpp"
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
-#include "../common/shmpipe.hpp"
-#include "../server/framebuf.hpp"
+#include "../common/bsocklink.hpp"
 #include "protocol.hpp"
 #include "replyruns.hpp"
 
@@ -199,13 +198,12 @@ constexpr size_t kReadChunk = 65536;
 struct Backend {
     int id;
     std::string path;
-    int fd = -1;
     bool ok = false;
-    /* rests at one event's reads (the loop stops at the first read
-     * that ends past the quota) plus a partial frame */
-    FrameBuf in{kMaxReadPerEvent + 2 * kReadChunk};
-    std::string out;
-    bool writeBlocked = false;
+    /* The connection: socket, buffers and, once SHM_OK has answered
+     * our offer, the rings (bsocklink.hpp). `in` rests at one event's
+     * reads (the loop stops at the first read that ends past the
+     * quota) plus a partial frame. */
+    BsockLink link{kMaxReadPerEvent + 2 * kReadChunk};
     uint32_t nextReq = 1;
     std::unique_ptr<PendingSlot[]> pending;  /* lazily sized ring */
     size_t pendingCount = 0;
@@ -218,21 +216,8 @@ struct Backend {
      * request will be silently dropped, so overloads must be visible
      * on the stats socket, not silent */
     uint64_t overwrites = 0;
-    size_t outOff = 0;  /* consumed prefix of `out` (flush cursor) */
     size_t sweepCursor = 0;  /* incremental pending-expiry scan */
     size_t remotes = 0;
-
-    /* Shared-memory rings for this connection (protocol.hpp, types
-     * 5-7). shmOffered: the region exists and the offer went out.
-     * rxShm: SHM_OK seen, replies are taken from the reply ring.
-     * streamEnd: end of the SHM_GO frame in `out`; bytes before it
-     * still go to the socket, and once they have, txShm is set and
-     * everything after goes to the query ring. */
-    shm::Link shm;
-    bool shmOffered = false;
-    bool rxShm = false;
-    bool txShm = false;
-    size_t streamEnd = 0;
 
     PendingSlot* slotFor(uint32_t reqId) {
         if (!pending) {
@@ -283,10 +268,8 @@ class Balancer {
     void onBackendBell(std::shared_ptr<Backend> be);
     void serveBackend(Backend* be, bool fromRing);
     void offerShm(Backend* be);
-    void dropShm(Backend* be);
     EventLoop::Park beforePark(bool park);
     void backendFlush(Backend* be);
-    void flushToRing(Backend* be);
     Backend* pickBackend(const std::string& remoteIp);
     Backend* pickBackendFast(const struct sockaddr_storage& ss);
     Backend* chooseLeastLoaded();
@@ -432,6 +415,18 @@ class Balancer {
             }
         }
     };
+    /* what a backend's link leaves to its owner (bsocklink.hpp) */
+    struct LinkSink {
+        Balancer* b;
+        int fd;
+        void armWrite() { b->loop_->modFd(fd, EPOLLIN | EPOLLOUT); }
+        void disarmWrite() { b->loop_->modFd(fd, EPOLLIN); }
+        void doorbell() { b->shmDoorbells_++; }
+        void drained() {
+            b->backendReads_++;
+            b->shmDrains_++;
+        }
+    };
     UdpSink udpSink_{&udpFd_};
     ReplyRuns<UdpSink> replyRuns_{udpSink_};
 };
@@ -565,7 +560,7 @@ void Balancer::rescan() {
                 connectBackend(be.get());
             } else {
                 Backend* be = backends_[full].get();
-                if (be->fd < 0) connectBackend(be);  // retry
+                if (be->link.fd < 0) connectBackend(be);  // retry
             }
         }
     }
@@ -597,7 +592,7 @@ void Balancer::connectBackend(Backend* be) {
         be->ok = false;
         return;
     }
-    be->fd = fd;
+    be->link.fd = fd;
     be->ok = true;  // optimistic; PING confirms
     be->lastPongAt = monotonicMillis();
     auto self = backendsById_[be->id];
@@ -613,7 +608,7 @@ void Balancer::connectBackend(Backend* be) {
  * descriptors. Any failure leaves the connection on the stream. */
 void Balancer::offerShm(Backend* be) {
     int fds[bsock::kShmOfferFds] = {-1, -1, -1};
-    fds[0] = be->shm.region.create(g_shmRing);
+    fds[0] = be->link.shm.region.create(g_shmRing);
     if (fds[0] >= 0) {
         fds[1] = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC);
         fds[2] = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC);
@@ -646,7 +641,8 @@ void Balancer::offerShm(Backend* be) {
         cm->cmsg_len = CMSG_LEN(sizeof(fds));
         memcpy(CMSG_DATA(cm), fds, sizeof(fds));
         /* 18 bytes into an empty send buffer: all or nothing */
-        sent = sendmsg(be->fd, &mh, MSG_NOSIGNAL) == (ssize_t)sizeof(frame);
+        sent = sendmsg(be->link.fd, &mh, MSG_NOSIGNAL) ==
+               (ssize_t)sizeof(frame);
     }
     if (fds[0] >= 0) close(fds[0]);  /* mapped, and sent or useless */
     if (!sent) {
@@ -654,44 +650,38 @@ void Balancer::offerShm(Backend* be) {
                    "no shared-memory offer; staying on the stream");
         if (fds[1] >= 0) close(fds[1]);
         if (fds[2] >= 0) close(fds[2]);
-        be->shm.close();
+        be->link.shm.close();
         return;
     }
-    be->shm.wakePeer = fds[1];
-    be->shm.wakeMe = fds[2];
-    be->shm.attachEnds(true);
-    be->shmOffered = true;
+    be->link.shm.wakePeer = fds[1];
+    be->link.shm.wakeMe = fds[2];
+    be->link.shm.attachEnds(true);
+    be->link.shmReady = true;
     auto self = backendsById_[be->id];
-    loop_->addFd(be->shm.wakeMe, EPOLLIN | EPOLLET,
+    loop_->addFd(be->link.shm.wakeMe, EPOLLIN | EPOLLET,
                  [this, self](uint32_t) { onBackendBell(self); });
 }
 
-void Balancer::dropShm(Backend* be) {
-    if (be->shmOffered) loop_->delFd(be->shm.wakeMe);
-    be->shm.close();
-    be->shmOffered = be->rxShm = be->txShm = false;
-    be->streamEnd = 0;
-}
-
 void Balancer::backendDown(Backend* be) {
-    if (be->fd >= 0) {
-        loop_->delFd(be->fd);
-        close(be->fd);
-        be->fd = -1;
+    if (be->link.fd >= 0) {
+        loop_->delFd(be->link.fd);
+        close(be->link.fd);
+        be->link.fd = -1;
     }
-    dropShm(be);
+    if (be->link.shmReady) loop_->delFd(be->link.shm.wakeMe);
+    be->link.dropRings();
     be->ok = false;
     dropRouteCache();
-    be->in.clear();
+    be->link.in.clear();
     /* Salvage: frames we queued but never flushed into the dead
      * connection can be re-dispatched to a healthy backend instead of
      * silently dropped — the client's in-flight query then survives a
      * backend crash (a query already inside the dead socket's buffer
      * is genuinely lost; the client retries). */
-    std::string unsent = be->out.substr(be->outOff);
-    be->out.clear();
-    be->outOff = 0;
-    be->writeBlocked = false;
+    std::string unsent = be->link.out.substr(be->link.outOff);
+    be->link.out.clear();
+    be->link.outOff = 0;
+    be->link.writeBlocked = false;
     be->clearPending();
     /* unpin remotes so they re-pick a healthy backend */
     for (auto it = remotes_.begin(); it != remotes_.end();) {
@@ -755,107 +745,27 @@ void Balancer::backendDown(Backend* be) {
     }
 }
 
-/* Query bytes into the ring: what fits now; the rest stays in `out`
- * and the backend rings our doorbell when it has made room. */
-void Balancer::flushToRing(Backend* be) {
-    bool wrote = false;
-    be->writeBlocked = false;
-    while (be->outOff < be->out.size()) {
-        size_t n = be->shm.tx.write(be->out.data() + be->outOff,
-                                    be->out.size() - be->outOff);
-        be->outOff += n;
-        if (n != 0) wrote = true;
-        if (be->outOff >= be->out.size()) break;
-        if (be->shm.tx.bad()) {
-            log_.warn({{"path", Json(be->path)}},
-                      "backend corrupted the query ring");
-            backendDown(be);
-            return;
-        }
-        if (be->shm.tx.waitForSpace()) {
-            be->writeBlocked = true;
-            break;
-        }
-    }
-    if (wrote && be->shm.tx.consumerNeedsWake()) {
-        shm::ringDoorbell(be->shm.wakePeer);
-        shmDoorbells_++;
-    }
-    if (be->outOff >= be->out.size()) {
-        be->out.clear();
-        be->outOff = 0;
-    } else if (be->outOff > (1u << 20)) {
-        be->out.erase(0, be->outOff);
-        be->outOff = 0;
-    }
-}
-
 void Balancer::backendFlush(Backend* be) {
-    if (be->txShm) {
-        if (be->fd >= 0) flushToRing(be);
-        return;
-    }
-    /* with a SHM_GO queued, the stream gets the bytes up to its end */
-    while (be->fd >= 0) {
-        size_t end = be->streamEnd != 0 ? be->streamEnd : be->out.size();
-        if (be->outOff >= end) break;
-        ssize_t nw = write(be->fd, be->out.data() + be->outOff,
-                           end - be->outOff);
-        if (nw > 0) {
-            be->outOff += (size_t)nw;
-            continue;
-        }
-        if (nw < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
-            /* compact occasionally so a long-blocked backend does not
-             * keep a consumed prefix resident (amortized O(1) vs the
-             * O(n) memmove-per-write of erase(0, nw)) */
-            if (be->outOff > (1u << 20)) {
-                be->out.erase(0, be->outOff);
-                if (be->streamEnd != 0) be->streamEnd -= be->outOff;
-                be->outOff = 0;
-            }
-            if (!be->writeBlocked) {
-                be->writeBlocked = true;
-                loop_->modFd(be->fd, EPOLLIN | EPOLLOUT);
-            }
-            return;
-        }
+    if (be->link.fd < 0) return;
+    BsockLink::Flush r = be->link.flush(LinkSink{this, be->link.fd});
+    if (r == BsockLink::Flush::RingBad)
+        log_.warn({{"path", Json(be->path)}},
+                  "backend corrupted the query ring");
+    if (r == BsockLink::Flush::RingBad || r == BsockLink::Flush::StreamError)
         backendDown(be);
-        return;
-    }
-    if (be->fd < 0) return;
-    if (be->writeBlocked) {
-        be->writeBlocked = false;
-        loop_->modFd(be->fd, EPOLLIN);
-    }
-    if (be->streamEnd != 0 && be->outOff >= be->streamEnd) {
-        /* SHM_GO is on the wire: the ring from here on */
-        be->streamEnd = 0;
-        be->txShm = true;
-        flushToRing(be);
-        return;
-    }
-    if (be->outOff >= be->out.size()) {
-        be->out.clear();
-        be->outOff = 0;
-    }
 }
 
 void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
-    if (be->fd < 0) return;
+    if (be->link.fd < 0) return;
     if (ev & (EPOLLHUP | EPOLLERR)) {
         log_.warn({{"path", Json(be->path)}}, "backend connection lost");
         backendDown(be.get());
         return;
     }
     if (ev & EPOLLOUT) backendFlush(be.get());
-    if (!(ev & EPOLLIN) || be->fd < 0) return;
-    if (be->rxShm) {
-        /* SHM_OK was the backend's last word on the stream: all that
-         * can show up here now is its end, or a peer gone wrong */
-        char junk[64];
-        ssize_t nr = read(be->fd, junk, sizeof(junk));
-        if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return;
+    if (!(ev & EPOLLIN) || be->link.fd < 0) return;
+    if (be->link.rxShm) {
+        if (be->link.streamStillOpen()) return;
         log_.warn({{"path", Json(be->path)}}, "backend closed connection");
         backendDown(be.get());
         return;
@@ -866,9 +776,9 @@ void Balancer::onBackendEvent(std::shared_ptr<Backend> be, uint32_t ev) {
 /* the backend's doorbell: replies in the ring, or room in the query
  * ring we were waiting for (edge-triggered; the eventfd is not read) */
 void Balancer::onBackendBell(std::shared_ptr<Backend> be) {
-    if (be->fd < 0 || !be->shmOffered) return;
-    if (be->txShm && be->writeBlocked) backendFlush(be.get());
-    if (be->fd >= 0 && be->rxShm) serveBackend(be.get(), true);
+    if (be->link.fd < 0 || !be->link.shmReady) return;
+    if (be->link.bellWantsFlush()) backendFlush(be.get());
+    if (be->link.fd >= 0 && be->link.rxShm) serveBackend(be.get(), true);
 }
 
 /* The loop's hook (loop.hpp). Every round: take what the reply rings
@@ -877,14 +787,11 @@ void Balancer::onBackendBell(std::shared_ptr<Backend> be) {
 EventLoop::Park Balancer::beforePark(bool park) {
     EventLoop::Park out = EventLoop::Park::NoRings;
     for (auto& [id, be] : backendsById_) {
-        if (!be->rxShm || be->fd < 0) continue;
-        if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
-        if (park) {
-            if (!be->shm.rx.park()) out = EventLoop::Park::Work;
-        } else if (be->shm.rx.readable() != 0 || be->shm.rx.bad()) {
+        if (be->link.fd < 0) continue;
+        EventLoop::Park s = be->link.parkState<EventLoop::Park>(park);
+        if (s == EventLoop::Park::Work && !park)
             serveBackend(be.get(), true);
-            out = EventLoop::Park::Work;
-        }
+        if (s > out) out = s;
     }
     return out;
 }
@@ -895,20 +802,22 @@ void Balancer::serveBackend(Backend* be, bool fromRing) {
      * read that used to end every event is not made. A ring is drained
      * the same way, to the same quota. */
     size_t got = 0;
-    while (got < kMaxReadPerEvent) {
-        if (fromRing) {
-            size_t n = be->shm.rx.read(be->in.tail(kReadChunk), kReadChunk);
-            if (n == 0) break;
-            be->in.commit(n);
-            got += n;
-            backendReads_++;
-            shmDrains_++;
-            if (n < kReadChunk) break;
-            continue;
+    if (fromRing) {
+        got = be->link.drainRing(kMaxReadPerEvent, kReadChunk,
+                                 LinkSink{this, be->link.fd});
+        if (got == BsockLink::kRingBad) {
+            log_.warn({{"path", Json(be->path)}},
+                      "backend corrupted the reply ring");
+            backendDown(be);
+            return;
         }
-        ssize_t nr = read(be->fd, be->in.tail(kReadChunk), kReadChunk);
+        if (got == 0) return;
+    }
+    while (!fromRing && got < kMaxReadPerEvent) {
+        ssize_t nr = read(be->link.fd, be->link.in.tail(kReadChunk),
+                          kReadChunk);
         if (nr > 0) {
-            be->in.commit((size_t)nr);
+            be->link.in.commit((size_t)nr);
             got += (size_t)nr;
             backendReads_++;
             if ((size_t)nr < kReadChunk) break;
@@ -919,19 +828,6 @@ void Balancer::serveBackend(Backend* be, bool fromRing) {
         backendDown(be);
         return;
     }
-    if (fromRing) {
-        if (be->shm.rx.bad()) {
-            log_.warn({{"path", Json(be->path)}},
-                      "backend corrupted the reply ring");
-            backendDown(be);
-            return;
-        }
-        if (got == 0) return;
-        if (be->shm.rx.producerNeedsWake()) {
-            shm::ringDoorbell(be->shm.wakePeer);
-            shmDoorbells_++;
-        }
-    }
 
     /* Walk the complete frames. UDP replies are filed into reply runs
      * as they are parsed (replyruns.hpp): same-destination equal-size
@@ -939,14 +835,14 @@ void Balancer::serveBackend(Backend* be, bool fromRing) {
      * the rest through one sendmmsg batch, and all of them before this
      * handler returns.
      *
-     * Invariant: the iovecs held by replyRuns_ point into be->in. All
+     * Invariant: the iovecs held by replyRuns_ point into be->link.in. All
      * reads of the event are done (above), and nothing may move or
      * reuse that buffer - no tail(), compact(), clear(), so no
      * backendDown() either - until replyRuns_.finish() has run. */
     bool bad = false, sawOk = false;
     for (;;) {
         bsock::FrameView f;
-        bsock::FrameStatus st = bsock::nextFrame(be->in, f);
+        bsock::FrameStatus st = bsock::nextFrame(be->link.in, f);
         if (st == bsock::FrameStatus::NeedMore) break;
         if (st == bsock::FrameStatus::Bad) {
             bad = true;
@@ -956,16 +852,15 @@ void Balancer::serveBackend(Backend* be, bool fromRing) {
             be->lastPongAt = monotonicMillis();
             be->ok = true;
         } else if (f.type == bsock::FRAME_SHM_OK) {
-            if (!be->shmOffered || be->rxShm) {
+            if (!be->link.shmReady || be->link.rxShm) {
                 bad = true;  /* nothing was offered, or twice */
                 break;
             }
             /* the backend's replies continue in the ring; ours follow
              * this SHM_GO there, once the stream has carried it */
-            be->rxShm = true;
+            be->link.rxShm = true;
             sawOk = true;
-            bsock::appendFrame(be->out, bsock::FRAME_SHM_GO, "");
-            be->streamEnd = be->out.size();
+            be->link.queueSwitch(bsock::FRAME_SHM_GO);
         } else if (f.type == bsock::FRAME_REPLY && f.plen >= 4) {
             uint32_t reqId = bsock::getU32(f.payload);
             PendingSlot* pr = be->slotFor(reqId);
@@ -996,14 +891,14 @@ void Balancer::serveBackend(Backend* be, bool fromRing) {
     replyRuns_.finish();
     /* SHM_OK ends the stream: a partial frame behind it can never be
      * completed */
-    if (sawOk && be->in.size() != 0) bad = true;
+    if (sawOk && be->link.in.size() != 0) bad = true;
     if (bad) {
         /* wrong magic or an impossible length: the stream cannot be
          * resynced */
         backendDown(be);
         return;
     }
-    be->in.compact();
+    be->link.in.compact();
     if (sawOk) backendFlush(be);
 }
 
@@ -1026,7 +921,7 @@ Backend* Balancer::chooseLeastLoaded() {
     int idx = 0;
     for (auto& [id, be] : backendsById_) {
         int i = idx++;
-        if (!be->ok || be->fd < 0) continue;
+        if (!be->ok || be->link.fd < 0) continue;
         bool preferred =
             nWorkers_ >= nb ? (workerId_ % (nb > 0 ? nb : 1)) == i
                             : (i % nWorkers_) == workerId_;
@@ -1211,7 +1106,7 @@ void Balancer::handleUdpQuery(const uint8_t* dns, size_t dnsLen,
      * client deadline — drop now (clients retry) rather than queue
      * into a multi-ms tail */
     if (be->pendingCount > kMaxPending ||
-        be->out.size() - be->outOff > (4u << 20)) {
+        be->link.out.size() - be->link.outOff > (4u << 20)) {
         drops_++;
         return;
     }
@@ -1262,7 +1157,7 @@ void Balancer::handleUdpQuery(const uint8_t* dns, size_t dnsLen,
         pr->srcPort = p;
         memcpy(pr->addr, &sa->sin6_addr, 16);
     }
-    std::string& o = be->out;
+    std::string& o = be->link.out;
     o.append((const char*)head, sizeof(head));
     o.append((const char*)dns, dnsLen);
     be->queries++;
@@ -1374,7 +1269,7 @@ void Balancer::onTcpClient(std::shared_ptr<TcpClient> c, uint32_t ev) {
             bsock::putU16(payload, srcPort);
             payload.append((const char*)addr16, 16);
             payload.append(c->in.data() + 2, mlen);
-            bsock::appendFrame(be->out, bsock::FRAME_QUERY, payload);
+            bsock::appendFrame(be->link.out, bsock::FRAME_QUERY, payload);
             be->queries++;
             backendFlush(be);
         }
@@ -1396,7 +1291,7 @@ Json Balancer::snapshot() const {
         b.set("pending", Json((int64_t)be->pendingCount));
         b.set("overwrites", Json((int64_t)be->overwrites));
         b.set("transport",
-              Json(std::string(be->rxShm && be->txShm ? "shm"
+              Json(std::string(be->link.rxShm && be->link.txShm ? "shm"
                                                       : "stream")));
         bes.push_back(std::move(b));
     }
@@ -1524,7 +1419,7 @@ void Balancer::sweep() {
         tcpClients_.erase(c->fd);
     }
     for (auto& [path, be] : backends_) {
-        if (be->fd < 0) continue;
+        if (be->link.fd < 0) continue;
         /* Expire stale pendings (uint32 wrap-safe comparison) in a
          * bounded chunk per tick: a full walk of the ring is ~8 MB of
          * cold cache per backend and was measured as a multi-ms stall
@@ -1552,7 +1447,7 @@ void Balancer::sweep() {
         }
         /* health probe */
         if (now - be->pingSentAt >= kPingIntervalMs) {
-            bsock::appendFrame(be->out, bsock::FRAME_PING, "");
+            bsock::appendFrame(be->link.out, bsock::FRAME_PING, "");
             be->pingSentAt = now;
             backendFlush(be.get());
         }

@@ -1019,7 +1019,7 @@ std::function<void(std::vector<uint8_t>)> DnsServer::makeAsyncReply(
         auto deliver = [this, self, ctx, reqId](
                            const std::vector<uint8_t>& w) {
             if (self->closed) return;
-            appendReplyFrame(self->out, reqId, w.data(), w.size());
+            appendReplyFrame(self->link.out, reqId, w.data(), w.size());
             balFlush(*ctx, self.get());
         };
         if (ctx->loop->inLoopThread()) {
@@ -1389,7 +1389,7 @@ void DnsServer::onBalAccept() {
 void DnsServer::adoptBal(ServeCtx& ctx, int fd) {
     auto conn = std::make_shared<BalConn>();
     conn->ctx = &ctx;
-    conn->fd = fd;
+    conn->link.fd = fd;
     BalConn* raw = conn.get();
     ctx.balConns[fd] = std::move(conn);
     ServeCtx* cp = &ctx;
@@ -1410,17 +1410,16 @@ void DnsServer::dropRxFds(BalConn* c) {
 void DnsServer::closeBal(ServeCtx& ctx, BalConn* c) {
     if (c->closed) return;
     c->closed = true;
-    ctx.loop->delFd(c->fd);
-    close(c->fd);
-    if (c->shmOn) {
-        ctx.loop->delFd(c->shm.wakeMe);
+    ctx.loop->delFd(c->link.fd);
+    close(c->link.fd);
+    if (c->link.shmReady) {
+        ctx.loop->delFd(c->link.shm.wakeMe);
         auto& v = ctx.shmConns;
         v.erase(std::remove(v.begin(), v.end(), c), v.end());
-        c->shmOn = c->rxShm = c->txShm = false;
     }
-    c->shm.close();
+    c->link.dropRings();
     dropRxFds(c);
-    ctx.balConns.erase(c->fd);
+    ctx.balConns.erase(c->link.fd);
 }
 
 /* SHM_OFFER, at its place in the batch. Accepting means: map the region
@@ -1430,12 +1429,13 @@ void DnsServer::closeBal(ServeCtx& ctx, BalConn* c) {
  * never hearing SHM_OK, stays on the stream. */
 void DnsServer::acceptShm(ServeCtx& ctx, BalConn* c, const uint8_t* p,
                           size_t len) {
-    bool ok = opts_.balancerShm && !c->shmOn &&
+    shm::Link& rings = c->link.shm;
+    bool ok = opts_.balancerShm && !c->link.shmReady &&
               c->nRxFds == bsock::kShmOfferFds &&
               len >= bsock::kShmOfferLen &&
               bsock::getU32(p) == shm::kVersion &&
               bsock::getU32(p + 8) == shm::kDataOff &&
-              c->shm.region.attach(c->rxFds[0], bsock::getU32(p + 4)) &&
+              rings.region.attach(c->rxFds[0], bsock::getU32(p + 4)) &&
               setNonBlocking(c->rxFds[1]) && setNonBlocking(c->rxFds[2]);
     if (ok) {
         BalConn* raw = c;
@@ -1451,110 +1451,44 @@ void DnsServer::acceptShm(ServeCtx& ctx, BalConn* c, const uint8_t* p,
     }
     if (!ok) {
         log_.debug("shared-memory offer declined");
-        c->shm.region.reset();
+        rings.region.reset();
         dropRxFds(c);
         return;
     }
     close(c->rxFds[0]);  /* mapped */
-    c->shm.wakeMe = c->rxFds[1];
-    c->shm.wakePeer = c->rxFds[2];
+    rings.wakeMe = c->rxFds[1];
+    rings.wakePeer = c->rxFds[2];
     c->nRxFds = 0;
-    c->shm.attachEnds(false);
-    c->shmOn = true;
+    rings.attachEnds(false);
+    c->link.shmReady = true;
     ctx.shmConns.push_back(c);
-    bsock::appendFrame(c->out, bsock::FRAME_SHM_OK, "");
-    c->streamEnd = c->out.size();
+    c->link.queueSwitch(bsock::FRAME_SHM_OK);
 }
 
-/* Reply bytes into the ring: what fits now; the rest stays in `out`
- * and the balancer rings our doorbell when it has made room. */
-void DnsServer::flushToRing(ServeCtx& ctx, BalConn* c) {
-    bool wrote = false;
-    c->writeBlocked = false;
-    while (c->outOff < c->out.size()) {
-        size_t n = c->shm.tx.write(c->out.data() + c->outOff,
-                                   c->out.size() - c->outOff);
-        c->outOff += n;
-        if (n != 0) wrote = true;
-        if (c->outOff >= c->out.size()) break;
-        if (c->shm.tx.bad()) {
-            closeBal(ctx, c);
-            return;
-        }
-        if (c->shm.tx.waitForSpace()) {
-            c->writeBlocked = true;
-            break;
-        }
-    }
-    if (wrote && c->shm.tx.consumerNeedsWake()) {
-        shm::ringDoorbell(c->shm.wakePeer);
-        ctx.shmDoorbells.bump();
-    }
-    if (c->outOff >= c->out.size()) {
-        c->out.clear();
-        c->outOff = 0;
-    } else if (c->outOff > (1u << 20)) {
-        c->out.erase(0, c->outOff);
-        c->outOff = 0;
-    }
-}
+/* what a connection's link leaves to its owner (bsocklink.hpp) */
+struct DnsServer::LinkSink {
+    ServeCtx& ctx;
+    int fd;
+    void armWrite() { ctx.loop->modFd(fd, EPOLLIN | EPOLLOUT); }
+    void disarmWrite() { ctx.loop->modFd(fd, EPOLLIN); }
+    void doorbell() { ctx.shmDoorbells.bump(); }
+    void drained() { ctx.shmDrains.bump(); }
+};
 
 void DnsServer::balFlush(ServeCtx& ctx, BalConn* c) {
     if (c->closed) return;
-    if (c->txShm) {
-        flushToRing(ctx, c);
-        return;
-    }
-    /* with a SHM_OK queued, the stream gets the bytes up to its end */
-    while (true) {
-        size_t end = c->streamEnd != 0 ? c->streamEnd : c->out.size();
-        if (c->outOff >= end) break;
-        ssize_t nw = write(c->fd, c->out.data() + c->outOff,
-                           end - c->outOff);
-        if (nw > 0) {
-            c->outOff += (size_t)nw;
-            continue;
-        }
-        if (nw < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
-            /* compact only past a large flushed prefix, so a peer that
-             * stays blocked does not keep it resident (amortized O(1)
-             * against the memmove-per-write of erase(0, nw)) */
-            if (c->outOff > (1u << 20)) {
-                c->out.erase(0, c->outOff);
-                if (c->streamEnd != 0) c->streamEnd -= c->outOff;
-                c->outOff = 0;
-            }
-            if (!c->writeBlocked) {
-                c->writeBlocked = true;
-                ctx.loop->modFd(c->fd, EPOLLIN | EPOLLOUT);
-            }
-            return;
-        }
+    BsockLink::Flush r = c->link.flush(LinkSink{ctx, c->link.fd});
+    if (r == BsockLink::Flush::StreamError || r == BsockLink::Flush::RingBad)
         closeBal(ctx, c);
-        return;
-    }
-    if (c->writeBlocked) {
-        c->writeBlocked = false;
-        ctx.loop->modFd(c->fd, EPOLLIN);
-    }
-    if (c->streamEnd != 0) {
-        /* SHM_OK is on the wire: the ring from here on */
-        c->streamEnd = 0;
-        c->txShm = true;
-        flushToRing(ctx, c);
-        return;
-    }
-    c->out.clear();
-    c->outOff = 0;
 }
 
 /* the balancer's doorbell: queries in the ring, or room in the reply
- * ring we were waiting for (edge-triggered; the eventfd is not read) */
+ * ring we were waiting for */
 void DnsServer::onBalBell(ServeCtx& ctx, BalConn* c) {
     std::shared_ptr<BalConn> keep = c->shared_from_this();
     if (c->closed) return;
-    if (c->txShm && c->writeBlocked) balFlush(ctx, c);
-    if (!c->closed && c->rxShm) serveBal(ctx, c, true);
+    if (c->link.bellWantsFlush()) balFlush(ctx, c);
+    if (!c->closed && c->link.rxShm) serveBal(ctx, c, true);
 }
 
 /* The hook of ctx's loop (loop.hpp). Every round: serve what the query
@@ -1563,44 +1497,29 @@ void DnsServer::onBalBell(ServeCtx& ctx, BalConn* c) {
 EventLoop::Park DnsServer::balBeforePark(ServeCtx& ctx, bool park) {
     auto& v = ctx.shmConns;
     EventLoop::Park out = EventLoop::Park::NoRings;
-    if (park) {
-        for (BalConn* c : v) {
-            if (!c->rxShm) continue;
-            if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
-            if (!c->shm.rx.park()) out = EventLoop::Park::Work;
-        }
-        return out;
-    }
     for (size_t i = 0; i < v.size();) {
         BalConn* c = v[i];
-        if (c->rxShm) {
-            if (out == EventLoop::Park::NoRings) out = EventLoop::Park::Idle;
-            if (c->shm.rx.readable() != 0 || c->shm.rx.bad()) {
-                std::shared_ptr<BalConn> keep = c->shared_from_this();
-                serveBal(ctx, c, true);
-                out = EventLoop::Park::Work;
-            }
+        EventLoop::Park s = c->link.parkState<EventLoop::Park>(park);
+        if (s == EventLoop::Park::Work && !park) {
+            std::shared_ptr<BalConn> keep = c->shared_from_this();
+            serveBal(ctx, c, true);
         }
+        if (s > out) out = s;
         if (i < v.size() && v[i] == c) ++i;  /* else it was closed */
     }
     return out;
 }
 
 void DnsServer::onBalConn(ServeCtx& ctx, BalConn* c, uint32_t events) {
-    std::shared_ptr<BalConn> keep = ctx.balConns[c->fd];
+    std::shared_ptr<BalConn> keep = ctx.balConns[c->link.fd];
     if (events & (EPOLLHUP | EPOLLERR)) {
         closeBal(ctx, c);
         return;
     }
     if (events & EPOLLOUT) balFlush(ctx, c);
     if (c->closed || !(events & EPOLLIN)) return;
-    if (c->rxShm) {
-        /* SHM_GO was the balancer's last word on the stream: all that
-         * can show up here now is its end, or a peer gone wrong */
-        char junk[64];
-        ssize_t nr = read(c->fd, junk, sizeof(junk));
-        if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return;
-        closeBal(ctx, c);
+    if (c->link.rxShm) {
+        if (!c->link.streamStillOpen()) closeBal(ctx, c);
         return;
     }
     serveBal(ctx, c, false);
@@ -1628,25 +1547,19 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
         /* the same quota, copied to the same place; a ring drained
          * short of it is empty, and whatever is left is found by the
          * poll before this thread sleeps */
-        got = c->shm.rx.read(c->in.tail(kMaxReadPerEvent),
-                             kMaxReadPerEvent);
-        if (c->shm.rx.bad()) {
+        got = c->link.drainRing(kMaxReadPerEvent, kMaxReadPerEvent,
+                                LinkSink{ctx, c->link.fd});
+        if (got == BsockLink::kRingBad) {
             closeBal(ctx, c);
             return;
         }
         if (got == 0) return;
-        c->in.commit(got);
-        ctx.shmDrains.bump();
-        if (c->shm.rx.producerNeedsWake()) {
-            shm::ringDoorbell(c->shm.wakePeer);
-            ctx.shmDoorbells.bump();
-        }
     }
     while (!fromRing && got < kMaxReadPerEvent) {
         size_t want = kMaxReadPerEvent - got;
         /* recvmsg, not read: a SHM_OFFER brings descriptors, and they
          * arrive with the read that returns its first byte */
-        struct iovec iov = {c->in.tail(want), want};
+        struct iovec iov = {c->link.in.tail(want), want};
         alignas(struct cmsghdr) char
             cbuf[CMSG_SPACE(sizeof(int) * bsock::kShmOfferFds)];
         struct msghdr mh {};
@@ -1654,9 +1567,9 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
         mh.msg_iovlen = 1;
         mh.msg_control = cbuf;
         mh.msg_controllen = sizeof(cbuf);
-        const bool mayOffer = opts_.balancerShm && !c->shmOn;
-        ssize_t nr = mayOffer ? recvmsg(c->fd, &mh, MSG_CMSG_CLOEXEC)
-                              : read(c->fd, iov.iov_base, want);
+        const bool mayOffer = opts_.balancerShm && !c->link.shmReady;
+        ssize_t nr = mayOffer ? recvmsg(c->link.fd, &mh, MSG_CMSG_CLOEXEC)
+                              : read(c->link.fd, iov.iov_base, want);
         if (mayOffer && nr >= 0 && mh.msg_controllen != 0) {
             for (struct cmsghdr* cm = CMSG_FIRSTHDR(&mh); cm != nullptr;
                  cm = CMSG_NXTHDR(&mh, cm)) {
@@ -1679,7 +1592,7 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
             }
         }
         if (nr > 0) {
-            c->in.commit((size_t)nr);
+            c->link.in.commit((size_t)nr);
             got += (size_t)nr;
             if ((size_t)nr < want) break;
             continue;
@@ -1712,7 +1625,7 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
     enum : uint8_t { kSkip, kPing, kQuery, kFastQuery, kShmOffer, kShmGo };
     struct PipeFrame {
         uint8_t kind;
-        const uint8_t* raw;  /* kShmOffer: payload, in c->in */
+        const uint8_t* raw;  /* kShmOffer: payload, in c->link.in */
         uint32_t rawLen;
         bsock::QueryFrame qf;
         FastQuery q;
@@ -1731,7 +1644,7 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
         while (st == bsock::FrameStatus::Ok &&
                fetched - served < kPipeDepth) {
             bsock::FrameView fr;
-            st = bsock::nextFrame(c->in, fr);
+            st = bsock::nextFrame(c->link.in, fr);
             if (st != bsock::FrameStatus::Ok) break;
             PipeFrame& p = ring[fetched++ & (kPipeDepth - 1)];
             p.off = AnswerTable::kNone;
@@ -1769,7 +1682,7 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
         /* stage 3: serve the oldest frame */
         PipeFrame& p = ring[served++ & (kPipeDepth - 1)];
         if (p.kind == kPing) {
-            bsock::appendFrame(c->out, bsock::FRAME_PONG, "");
+            bsock::appendFrame(c->link.out, bsock::FRAME_PONG, "");
             continue;
         }
         if (p.kind == kSkip) continue;
@@ -1780,11 +1693,12 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
         if (p.kind == kShmGo) {
             /* the balancer's queries continue in the ring (looked at
              * before this thread sleeps, at the latest) */
-            if (c->shmOn && !c->rxShm) c->rxShm = sawGo = true;
+            if (c->link.shmReady && !c->link.rxShm)
+                c->link.rxShm = sawGo = true;
             continue;
         }
         const bsock::QueryFrame& qf = p.qf;
-        ReplySink sink(&c->out, qf.reqId);
+        ReplySink sink(&c->link.out, qf.reqId);
         const bool udp = qf.proto == 0;
         if (p.kind == kFastQuery) {
             const uint8_t qt = p.q.isSrv ? 33 : 1;
@@ -1823,13 +1737,14 @@ void DnsServer::serveBal(ServeCtx& ctx, BalConn* c, bool fromRing) {
     }
     /* SHM_GO ends the stream: a partial frame behind it can never be
      * completed */
-    if (st == bsock::FrameStatus::Bad || (sawGo && c->in.size() != 0)) {
+    if (st == bsock::FrameStatus::Bad ||
+        (sawGo && c->link.in.size() != 0)) {
         closeBal(ctx, c);
         return;
     }
     /* a synchronous recursion reply may have hit a write error */
     if (c->closed) return;
-    c->in.compact();
+    c->link.in.compact();
     balFlush(ctx, c);
 }
 

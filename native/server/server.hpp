@@ -31,12 +31,11 @@
 #include <thread>
 #include <vector>
 
+#include "../common/bsocklink.hpp"
 #include "../common/log.hpp"
 #include "../common/loop.hpp"
-#include "../common/shmpipe.hpp"
 #include "../engine/engine.hpp"
 #include "answertab.hpp"
-#include "framebuf.hpp"
 #include "metrics.hpp"
 
 namespace bamd {
@@ -162,30 +161,16 @@ class DnsServer {
         int64_t lastActivityMs = 0;
     };
     struct ServeCtx;
-    struct BalConn : std::enable_shared_from_this<BalConn> {
+    struct LinkSink;
+    struct BalConn: std::enable_shared_from_this<BalConn> {
         ServeCtx* ctx = nullptr;  /* owner; only its thread touches us */
-        int fd;
-        FrameBuf in;
-        std::string out;
-        size_t outOff = 0;  /* flushed prefix of `out` (write cursor) */
-        bool writeBlocked = false;
+        /* socket, buffers and, once an offer is accepted, the rings */
+        BsockLink link;
         bool closed = false;
-
-        /* Shared-memory rings (protocol.hpp, types 5-7). rxFds: the
-         * descriptors that arrived with the stream bytes, until the
-         * SHM_OFFER frame they belong to is parsed. shmOn: the offer
-         * was accepted (region mapped, doorbell registered). streamEnd:
-         * end of the SHM_OK frame in `out`; bytes before it still go to
-         * the socket, and once they have, txShm is set and everything
-         * after goes to the reply ring. rxShm: SHM_GO seen, queries are
-         * taken from the query ring. */
-        shm::Link shm;
+        /* the descriptors that arrived with the stream bytes, until
+         * the SHM_OFFER frame they belong to is parsed */
         int rxFds[bsock::kShmOfferFds] = {-1, -1, -1};
         int nRxFds = 0;
-        bool shmOn = false;
-        bool rxShm = false;
-        bool txShm = false;
-        size_t streamEnd = 0;
         ~BalConn();
     };
 
@@ -218,7 +203,6 @@ class DnsServer {
     void serveBal(ServeCtx& ctx, BalConn* c, bool fromRing);
     void acceptShm(ServeCtx& ctx, BalConn* c, const uint8_t* p, size_t len);
     void dropRxFds(BalConn* c);
-    void flushToRing(ServeCtx& ctx, BalConn* c);
     EventLoop::Park balBeforePark(ServeCtx& ctx, bool park);
 
     /*
