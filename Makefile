@@ -180,6 +180,21 @@ $(BUILD)/bsocklink_check: native/common/bsocklink_check_main.cpp \
 check-bsocklink: $(BUILD)/bsocklink_check
 	$(BUILD)/bsocklink_check 1
 
+# Sanitizer run of the ZooKeeper connect-string parser (zk/hostlist.hpp)
+# in a stand-alone program: a fixed accept/reject table and seeded random
+# strings, each parsed from a heap block of exactly its length; what is
+# accepted is printed and parsed again and must give the same list.
+# Host-only, CPU-only.
+$(BUILD)/hostlist_check: native/zk/hostlist_check_main.cpp \
+		native/zk/hostlist.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-zkhosts: $(BUILD)/hostlist_check
+	$(BUILD)/hostlist_check 1 20000
+
 # ThreadSanitizer run of the serving-thread pool: binderd itself (a daemon
 # with its own main) built with -fsanitize=thread into $(BUILD)/tsan, and
 # the pool's tests plus the two suites that pin reply order and ingress
@@ -268,4 +283,4 @@ clean:
 
 .PHONY: all clean test check check-framebuf check-answertab \
 	check-replyruns check-shmpipe check-bsocklink check-serve-threads \
-	check-codec check-wire-asan release
+	check-codec check-wire-asan check-zkhosts release

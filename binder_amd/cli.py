@@ -220,8 +220,11 @@ def main(argv=None):
     p.add_argument("address")
     p.add_argument("-i", "--instance", default="binder0")
     p.add_argument("-p", "--port", type=int, default=53)
-    p.add_argument("--zk-host", default="127.0.0.1")
-    p.add_argument("--zk-port", type=int, default=2181)
+    p.add_argument("--zk-host", default="127.0.0.1",
+                   help="one server or a list host[:port],host[:port]; "
+                        "tried in order, the first that answers is used")
+    p.add_argument("--zk-port", type=int, default=2181,
+                   help="port of --zk-host entries that name none")
     p.add_argument("--hold", action="store_true",
                    help="ephemeral registration; stay attached as a "
                         "minimal registrar daemon")
@@ -237,8 +240,11 @@ def main(argv=None):
     p.add_argument("op", choices=["mkdirp", "rmr", "get", "ls", "set"])
     p.add_argument("path")
     p.add_argument("data", nargs="?")
-    p.add_argument("--zk-host", default="127.0.0.1")
-    p.add_argument("--zk-port", type=int, default=2181)
+    p.add_argument("--zk-host", default="127.0.0.1",
+                   help="one server or a list host[:port],host[:port]; "
+                        "tried in order, the first that answers is used")
+    p.add_argument("--zk-port", type=int, default=2181,
+                   help="port of --zk-host entries that name none")
     p.set_defaults(fn=cmd_zk)
 
     args = ap.parse_args(argv)

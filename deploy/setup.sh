@@ -17,7 +17,11 @@ CONFIG="${CONFIG:-$PREFIX/etc/config.json}"
 
 # Render config from a metadata file when provided (the reference's
 # config-agent step; sapi_manifests/binder/manifest.json).
+# ZK_SERVERS (`host[:port],host[:port]`) renders as zookeeper.servers,
+# the list binderd rotates over; unset, the config names no server and
+# binderd uses ZK_HOST.
 if [ -n "${METADATA:-}" ]; then
+    ZK_SERVERS="${ZK_SERVERS:-}" ZK_PORT="${ZK_PORT:-}" \
     python3 "$PREFIX/deploy/render-config.py" \
         "$PREFIX/etc/config.json.in" "$METADATA" > "$CONFIG"
 fi

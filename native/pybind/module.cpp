@@ -13,6 +13,7 @@
 #include "../dns/codec.hpp"
 #include "../engine/engine.hpp"
 #include "../engine/store.hpp"
+#include "../zk/hostlist.hpp"
 
 namespace py = pybind11;
 using namespace bamd;
@@ -336,6 +337,24 @@ PYBIND11_MODULE(_native, m) {
         if (!v) return py::none();
         return py::str(v->dump());
     });
+
+    /* the native connect-string parser (zk/hostlist.hpp), so that tests
+     * can hold binder_amd.zkclient.parse_hosts to it */
+    m.def("parse_zk_hosts",
+          [](const std::string& text, int defaultPort) {
+              if (defaultPort < 1 || defaultPort > 65535)
+                  throw py::value_error("default_port out of range");
+              std::vector<zk::ZkServer> servers;
+              std::string err;
+              if (!zk::parseHostList(text, (uint16_t)defaultPort, servers,
+                                     err))
+                  throw py::value_error(err);
+              py::list out;
+              for (const auto& s : servers)
+                  out.append(py::make_tuple(s.host, (int)s.port));
+              return out;
+          },
+          py::arg("text"), py::arg("default_port") = 2181);
 
     py::class_<PyStubEngine>(m, "StubEngine")
         .def(py::init<const std::string&, const std::string&, bool>(),

@@ -12,9 +12,11 @@
  * plus binder-amd extensions:
  *   -S <mode>  store mode: "zk" (default) or "file:<path>" (static JSON
  *              tree, used by tests/bench config 1)
- * Env: ZK_HOST (lib/zk.js:34), ZK_PORT (test/helper.js:54), LOG_LEVEL,
- * BINDER_SERVE_THREADS (overrides config key serveThreads; threads that
- * serve balancer connections, 1 = the main thread alone),
+ * Env: ZK_HOST (lib/zk.js:34; one server or a list `h[:p],h[:p]`, see
+ * zk/hostlist.hpp), ZK_PORT (test/helper.js:54; the port of entries
+ * without one), ZK_SHUFFLE (overrides config key zookeeper.shuffle),
+ * LOG_LEVEL, BINDER_SERVE_THREADS (overrides config key serveThreads;
+ * threads that serve balancer connections, 1 = the main thread alone),
  * BINDER_BAL_SHM (overrides config key balancerShm; 0 = decline a
  * balancer's offer of shared-memory rings and stay on the stream).
  * Option precedence: defaults < config file < CLI (main.js:105).
@@ -178,16 +180,49 @@ int main(int argc, char** argv) {
             log.fatal("dnsDomain is required with the zk store");
             return 1;
         }
+        /* Which servers: ZK_HOST, else zookeeper.servers ([{host, port}]
+         * as in the reference's registrar template), else zookeeper.host,
+         * else 127.0.0.1. ZK_HOST and zookeeper.host may be a list
+         * `h[:p],h[:p]`; ZK_PORT is the port of entries without one. */
         const char* zh = getenv("ZK_HOST");
         const char* zp = getenv("ZK_PORT");
-        std::string zkHost = zh && *zh ? zh : "127.0.0.1";
-        if (!zh && opts.get("zookeeper").isObject() &&
-            opts.get("zookeeper").get("host").isString())
-            zkHost = opts.get("zookeeper").get("host").asString();
         uint16_t zkPort = (uint16_t)(zp && *zp ? atoi(zp) : 2181);
-        mirror = std::make_unique<ZkMirror>(
-            &loop, log, ZkMirrorOptions{zkHost, zkPort, dnsDomain, 30000},
-            &collector);
+        const Json zkOpts = opts.get("zookeeper");
+        std::string zkList = "127.0.0.1";
+        if (zh) {
+            if (*zh) zkList = zh;
+        } else if (zkOpts.isObject() && zkOpts.get("servers").isArray()) {
+            zkList.clear();
+            for (const Json& s : zkOpts.get("servers").items()) {
+                if (!zkList.empty()) zkList += ',';
+                zkList += s.get("host").asString();
+                if (s.get("port").isNumber())
+                    zkList += ":" + std::to_string(s.get("port").asInt());
+            }
+        } else if (zkOpts.isObject() && zkOpts.get("host").isString()) {
+            zkList = zkOpts.get("host").asString();
+        }
+        ZkMirrorOptions zo;
+        zo.domain = dnsDomain;
+        std::string zkErr;
+        if (!zk::parseHostList(zkList, zkPort, zo.servers, zkErr)) {
+            log.log(LogLevel::Fatal,
+                    "malformed ZooKeeper server list: " + zkErr,
+                    {{"servers", Json(zkList)}});
+            return 1;
+        }
+        zo.host = zo.servers[0].host;
+        zo.port = zo.servers[0].port;
+        if (zkOpts.isObject() && zkOpts.get("connectTimeoutMs").isNumber())
+            zo.connectTimeoutMs =
+                (int)zkOpts.get("connectTimeoutMs").asInt();
+        /* many instances must not all land on the first member */
+        zo.shuffle = zo.servers.size() > 1;
+        if (zkOpts.isObject() && zkOpts.get("shuffle").isBool())
+            zo.shuffle = zkOpts.get("shuffle").asBool();
+        if (const char* e = getenv("ZK_SHUFFLE"); e && *e)
+            zo.shuffle = atoi(e) != 0;
+        mirror = std::make_unique<ZkMirror>(&loop, log, zo, &collector);
         mirror->start();
         store = mirror.get();
     } else {

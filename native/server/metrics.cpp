@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
+#include <string_view>
 
 namespace bamd {
 
@@ -82,6 +83,28 @@ Histogram* Collector::histogram(const std::string& name,
     return metrics_.back().histogram.get();
 }
 
+/* Calls f(name, pair) for every `name="value"` of a rendered label
+ * string (renderLabels' output: values escaped, pairs joined by ','). */
+template <typename F>
+static void eachLabel(const std::string& s, F f) {
+    size_t pos = 0;
+    while (pos < s.size()) {
+        size_t eq = s.find('=', pos);
+        if (eq == std::string::npos || eq + 1 >= s.size()) return;
+        size_t end = eq + 2;  /* past the opening quote */
+        while (end < s.size() && s[end] != '"')
+            end += s[end] == '\\' ? 2 : 1;
+        if (end >= s.size()) return;
+        f(std::string_view(s).substr(pos, eq - pos),
+          std::string_view(s).substr(pos, end + 1 - pos));
+        pos = end + 2;  /* past the closing quote and the comma */
+    }
+}
+
+/* a: the static labels, b: the series' own. A label name may appear
+ * once in a label set, so a series label wins over a static label of
+ * the same name (binder_zk_connect_failures' server="h:p" over the
+ * static server uuid). */
 static void appendLabelSet(std::string& out, const std::string& a,
                            const std::string& b,
                            const std::string& extra = "") {
@@ -89,7 +112,22 @@ static void appendLabelSet(std::string& out, const std::string& a,
     if (!any) return;
     out.push_back('{');
     bool first = true;
-    for (const std::string* s : {&a, &b, &extra}) {
+    if (!a.empty() && !b.empty()) {
+        eachLabel(a, [&](std::string_view name, std::string_view pair) {
+            bool shadowed = false;
+            eachLabel(b, [&](std::string_view own, std::string_view) {
+                shadowed = shadowed || own == name;
+            });
+            if (shadowed) return;
+            if (!first) out.push_back(',');
+            first = false;
+            out += pair;
+        });
+    } else if (!a.empty()) {
+        first = false;
+        out += a;
+    }
+    for (const std::string* s : {&b, &extra}) {
         if (s->empty()) continue;
         if (!first) out.push_back(',');
         first = false;

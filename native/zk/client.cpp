@@ -5,19 +5,52 @@
 #include <netinet/in.h>
 #include <netinet/tcp.h>
 #include <sys/epoll.h>
+#include <sys/random.h>
 #include <sys/socket.h>
 #include <unistd.h>
 
 #include <cstring>
+#include <utility>
 
 namespace bamd::zk {
 
 ZkClient::ZkClient(EventLoop* loop, Logger log, ZkConfig cfg)
     : loop_(loop),
       log_(log.child({{"component", Json("ZkClient")}})),
-      cfg_(std::move(cfg)) {}
+      cfg_(std::move(cfg)) {
+    servers_ = cfg_.servers;
+    if (servers_.empty()) servers_.push_back({cfg_.host, cfg_.port});
+    if (cfg_.shuffle && servers_.size() > 1) {
+        /* Fisher-Yates, drawn once per process from getrandom(2) so that
+         * every client of one process sees one order */
+        static const uint64_t kSeed = []() {
+            uint64_t s = 0;
+            if (getrandom(&s, sizeof(s), 0) != (ssize_t)sizeof(s))
+                s = (uint64_t)wallMillis() ^ ((uint64_t)getpid() << 32);
+            return s;
+        }();
+        uint64_t x = kSeed | 1;
+        for (size_t i = servers_.size() - 1; i > 0; i--) {
+            x ^= x << 13;  /* xorshift64 */
+            x ^= x >> 7;
+            x ^= x << 17;
+            std::swap(servers_[i], servers_[x % (i + 1)]);
+        }
+    }
+    for (const ZkServer& s : servers_) names_.push_back(serverName(s));
+}
 
 ZkClient::~ZkClient() { close(); }
+
+JsonObject ZkClient::serverField() const {
+    return {{"server", Json(names_[cur_])}};
+}
+
+int ZkClient::connectDeadlineMs() const {
+    if (cfg_.connectTimeoutMs > 0) return cfg_.connectTimeoutMs;
+    int t = cfg_.sessionTimeoutMs / (int)servers_.size();
+    return t > 0 ? t : 1;
+}
 
 void ZkClient::start() {
     closing_ = false;
@@ -47,6 +80,10 @@ void ZkClient::teardown() {
         loop_->cancelTimer(pingTimer_);
         pingTimer_ = 0;
     }
+    if (connectTimer_) {
+        loop_->cancelTimer(connectTimer_);
+        connectTimer_ = 0;
+    }
     if (fd_ >= 0) {
         loop_->delFd(fd_);
         ::close(fd_);
@@ -71,43 +108,62 @@ void ZkClient::failAllPending() {
     }
 }
 
-void ZkClient::scheduleReconnect() {
+void ZkClient::scheduleReconnect(int delayMs) {
     if (closing_ || reconnectTimer_) return;
     state_ = State::Closed;
     reconnects_++;
-    reconnectTimer_ = loop_->addTimer(cfg_.reconnectDelayMs, [this]() {
+    reconnectTimer_ = loop_->addTimer(delayMs, [this]() {
         reconnectTimer_ = 0;
         if (!closing_) connectStart();
     });
 }
 
+/* The current server failed us: move to the next and try it at once, or,
+ * when a whole pass over the list has failed, after reconnectDelayMs.
+ * The session credentials stay as they are. The next attempt starts from
+ * a zero-delay timer, not from here, so that no caller finds a new
+ * connection under its feet. */
+void ZkClient::serverFailed() {
+    teardown();
+    if (closing_ || reconnectTimer_) return;
+    if (failureCb_) failureCb_(names_[cur_]);
+    cur_ = (cur_ + 1) % servers_.size();
+    int delay = 0;
+    if (++failures_ >= servers_.size()) {
+        failures_ = 0;
+        delay = cfg_.reconnectDelayMs;
+    }
+    scheduleReconnect(delay);
+}
+
 void ZkClient::connectStart() {
     teardown();
     state_ = State::Connecting;
+    const ZkServer& srv = servers_[cur_];
     fd_ = socket(AF_INET, SOCK_STREAM | SOCK_NONBLOCK | SOCK_CLOEXEC, 0);
     if (fd_ < 0) {
-        scheduleReconnect();
+        serverFailed();
         return;
     }
     int one = 1;
     setsockopt(fd_, IPPROTO_TCP, TCP_NODELAY, &one, sizeof(one));
     struct sockaddr_in sa {};
     sa.sin_family = AF_INET;
-    sa.sin_port = htons(cfg_.port);
-    if (inet_pton(AF_INET, cfg_.host.c_str(), &sa.sin_addr) != 1) {
+    sa.sin_port = htons(srv.port);
+    if (inet_pton(AF_INET, srv.host.c_str(), &sa.sin_addr) != 1) {
         /* resolve hostnames (ZK_HOST may not be an IP); blocking, but
          * only on the (re)connect path */
         struct addrinfo hints {};
         hints.ai_family = AF_INET;
         hints.ai_socktype = SOCK_STREAM;
         struct addrinfo* res = nullptr;
-        int rc = getaddrinfo(cfg_.host.c_str(), nullptr, &hints, &res);
+        int rc = getaddrinfo(srv.host.c_str(), nullptr, &hints, &res);
         if (rc != 0 || res == nullptr) {
-            log_.error({{"host", Json(cfg_.host)}},
+            log_.error({{"host", Json(srv.host)},
+                        {"server", Json(names_[cur_])}},
                        "cannot resolve ZK host");
             if (res) freeaddrinfo(res);
-            teardown();
-            scheduleReconnect();
+            serverFailed();
             return;
         }
         sa.sin_addr = ((struct sockaddr_in*)res->ai_addr)->sin_addr;
@@ -115,12 +171,25 @@ void ZkClient::connectStart() {
     }
     int rv = ::connect(fd_, (struct sockaddr*)&sa, sizeof(sa));
     if (rv != 0 && errno != EINPROGRESS) {
-        teardown();
-        scheduleReconnect();
+        log_.debug(serverField(), "ZK connect failed; retrying");
+        serverFailed();
         return;
     }
     loop_->addFd(fd_, EPOLLIN | EPOLLOUT,
                  [this](uint32_t ev) { onSockEvent(ev); });
+    /* one deadline over TCP connect + ConnectResponse: a server that
+     * accepts and stays silent, or a black-holed address, must not park
+     * the client (the ping timer only runs once Connected) */
+    int deadline = connectDeadlineMs();
+    connectTimer_ = loop_->addTimer(deadline, [this, deadline]() {
+        connectTimer_ = 0;
+        if (state_ != State::Connecting && state_ != State::Handshaking)
+            return;
+        log_.warn({{"server", Json(names_[cur_])},
+                   {"timeoutMs", Json((int64_t)deadline)}},
+                  "ZK connect deadline expired");
+        serverFailed();
+    });
 }
 
 void ZkClient::sendHandshake() {
@@ -143,9 +212,8 @@ void ZkClient::onSockEvent(uint32_t events) {
         socklen_t elen = sizeof(err);
         getsockopt(fd_, SOL_SOCKET, SO_ERROR, &err, &elen);
         if (err != 0 || (events & (EPOLLERR | EPOLLHUP))) {
-            log_.debug("ZK connect failed; retrying");
-            teardown();
-            scheduleReconnect();
+            log_.debug(serverField(), "ZK connect failed; retrying");
+            serverFailed();
             return;
         }
         loop_->modFd(fd_, EPOLLIN);
@@ -153,9 +221,8 @@ void ZkClient::onSockEvent(uint32_t events) {
         return;
     }
     if (events & (EPOLLERR | EPOLLHUP)) {
-        log_.warn("ZK connection lost");
-        teardown();
-        scheduleReconnect();
+        log_.warn(serverField(), "ZK connection lost");
+        serverFailed();
         return;
     }
     if (events & EPOLLOUT) {
@@ -175,11 +242,8 @@ void ZkClient::onReadable() {
             continue;
         }
         if (nr < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
-        log_.warn("ZK connection closed by server");
-        bool hadSession = sessionId_ != 0;
-        teardown();
-        (void)hadSession;
-        scheduleReconnect();
+        log_.warn(serverField(), "ZK connection closed by server");
+        serverFailed();
         return;
     }
     lastPacketRecvMs_ = monotonicMillis();
@@ -190,9 +254,9 @@ void ZkClient::onReadable() {
                         ((uint32_t)(uint8_t)inBuf_[2] << 8) |
                         (uint32_t)(uint8_t)inBuf_[3];
         if (plen > (64u << 20)) {
-            log_.error("ZK packet too large; dropping connection");
-            teardown();
-            scheduleReconnect();
+            log_.error(serverField(),
+                       "ZK packet too large; dropping connection");
+            serverFailed();
             return;
         }
         if (inBuf_.size() < 4 + plen) break;
@@ -218,19 +282,22 @@ void ZkClient::onConnectResponse(const uint8_t* data, size_t len) {
      * a session verdict — reconnect WITHOUT discarding the session so
      * a later healthy server can still resume it. */
     if (!r.ok || proto != 0 || timeout > 600000) {
-        log_.warn("malformed ZK connect response; reconnecting");
-        teardown();
-        scheduleReconnect();
+        log_.warn(serverField(),
+                  "malformed ZK connect response; reconnecting");
+        serverFailed();
         return;
     }
     if (timeout <= 0 || sid == 0) {
-        /* session expired (server refuses resume): start a fresh one */
-        log_.warn("ZK session expired; creating a new session");
+        /* session expired (server refuses resume): start a fresh one.
+         * This is a healthy server's verdict, not a failure: stay on it */
+        log_.warn(serverField(),
+                  "ZK session expired; creating a new session");
         sessionId_ = 0;
         passwd_.clear();
         lastZxid_ = 0;
+        failures_ = 0;
         teardown();
-        scheduleReconnect();
+        scheduleReconnect(cfg_.reconnectDelayMs);
         return;
     }
     bool isNew = sid != sessionId_;
@@ -239,9 +306,19 @@ void ZkClient::onConnectResponse(const uint8_t* data, size_t len) {
     negotiatedTimeout_ = timeout;
     state_ = State::Connected;
     sessions_++;
+    if (connectTimer_) {
+        loop_->cancelTimer(connectTimer_);
+        connectTimer_ = 0;
+    }
+    /* a lost established connection is the first failure of its pass */
+    failures_ = 0;
+    if (lastSessionServer_ >= 0 && (size_t)lastSessionServer_ != cur_)
+        switches_++;
+    lastSessionServer_ = (int)cur_;
     log_.info({{"sessionId", Json((int64_t)sid)},
                {"timeout", Json((int64_t)timeout)},
-               {"new", Json(isNew)}},
+               {"new", Json(isNew)},
+               {"server", Json(names_[cur_])}},
               "ZK session established");
     armPingTimer();
     /* 'session' fires on every usable (re)connection — the mirror above
@@ -260,9 +337,9 @@ void ZkClient::armPingTimer() {
         int tt = negotiatedTimeout_ > 0 ? negotiatedTimeout_
                                         : cfg_.sessionTimeoutMs;
         if (silent > tt) {
-            log_.warn("ZK server unresponsive; reconnecting");
-            teardown();
-            scheduleReconnect();
+            log_.warn(serverField(),
+                      "ZK server unresponsive; reconnecting");
+            serverFailed();
             return;
         }
         sendPing();
@@ -299,8 +376,8 @@ void ZkClient::flush() {
             }
             return;
         }
-        teardown();
-        scheduleReconnect();
+        log_.debug(serverField(), "ZK write failed; retrying");
+        serverFailed();
         return;
     }
 }

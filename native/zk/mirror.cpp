@@ -33,6 +33,9 @@ ZkMirror::ZkMirror(EventLoop* loop, Logger log, ZkMirrorOptions opts,
     zc.host = opts_.host;
     zc.port = opts_.port;
     zc.sessionTimeoutMs = opts_.sessionTimeoutMs;
+    zc.servers = opts_.servers;
+    zc.connectTimeoutMs = opts_.connectTimeoutMs;
+    zc.shuffle = opts_.shuffle;
     client_ = std::make_unique<ZkClient>(loop_, log_, zc);
     client_->onSession([this]() { rebuild(); });
     client_->onWatch([this](int32_t type, const std::string& path) {
@@ -44,6 +47,16 @@ ZkMirror::ZkMirror(EventLoop* loop, Logger log, ZkMirrorOptions opts,
         sessionsCounter_ =
             collector->counter("binder_zk_sessions_established",
                                "ZooKeeper sessions established");
+        connectFailures_ = collector->counter(
+            "binder_zk_connect_failures",
+            "times a ZooKeeper server failed this client, by server");
+        serverSwitches_ = collector->counter(
+            "binder_zk_server_switches",
+            "ZooKeeper sessions established on another server than "
+            "the previous one");
+        client_->onServerFailure([this](const std::string& server) {
+            connectFailures_->increment(renderLabels({{"server", server}}));
+        });
     }
 }
 
@@ -83,6 +96,11 @@ ZkMirror::Node* ZkMirror::nodeAt(const std::string& path) {
 
 void ZkMirror::rebuild() {
     if (sessionsCounter_) sessionsCounter_->increment("");
+    if (serverSwitches_ != nullptr) {
+        uint64_t now = client_->serverSwitches();
+        serverSwitches_->increment("", now - switchesSeen_);
+        switchesSeen_ = now;
+    }
     if (root_ == nullptr) {
         auto n = std::make_unique<Node>(this, opts_.domain);
         root_ = n.get();

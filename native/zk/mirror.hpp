@@ -31,6 +31,11 @@ struct ZkMirrorOptions {
     uint16_t port = 2181;
     std::string domain;          // dnsDomain, e.g. "foo.com"
     int sessionTimeoutMs = 30000;
+    /* the server list and its knobs, as in zk::ZkConfig: an empty list
+     * means the one server {host, port} */
+    std::vector<zk::ZkServer> servers;
+    int connectTimeoutMs = 0;
+    bool shuffle = false;
 };
 
 class ZkMirror : public Store {
@@ -94,6 +99,9 @@ class ZkMirror : public Store {
 
     Counter* nodesGauge_ = nullptr;
     Counter* sessionsCounter_ = nullptr;
+    Counter* connectFailures_ = nullptr;  // labelled server="h:p"
+    Counter* serverSwitches_ = nullptr;
+    uint64_t switchesSeen_ = 0;
 };
 
 }  // namespace bamd

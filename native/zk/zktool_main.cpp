@@ -3,8 +3,10 @@
  * (zkCli-style operator tool; the reference leans on zkCli.sh from the
  * bundled ZooKeeper distribution for the same purpose).
  *
- * usage: zktool [-s host:port] <op> <path> [data]
+ * usage: zktool [-s host[:port][,host[:port]...]] <op> <path> [data]
  *   ops: get | ls | create | set | rm | rmr | stat
+ * A server list (zk/hostlist.hpp) is tried in the order given, never
+ * shuffled; the first server that gives a session serves the op.
  * Exit: 0 ok, 1 usage/connect error, 2 op error (e.g. no such node).
  */
 #include <unistd.h>
@@ -44,11 +46,11 @@ struct Ctx {
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string server = "127.0.0.1:2181";
+    std::string server = "127.0.0.1";
     const char* zh = getenv("ZK_HOST");
     const char* zp = getenv("ZK_PORT");
-    if (zh && *zh)
-        server = std::string(zh) + ":" + (zp && *zp ? zp : "2181");
+    if (zh && *zh) server = zh;
+    uint16_t defaultPort = (uint16_t)(zp && *zp ? atoi(zp) : 2181);
     int c;
     while ((c = getopt(argc, argv, "hs:")) != -1) {
         switch (c) {
@@ -56,7 +58,7 @@ int main(int argc, char** argv) {
         case 'h':
         default:
             fprintf(stderr,
-                    "usage: zktool [-s host:port] "
+                    "usage: zktool [-s host[:port][,host[:port]...]] "
                     "get|ls|create|set|rm|rmr|stat <path> [data]\n");
             return c == 'h' ? 0 : 1;
         }
@@ -70,13 +72,14 @@ int main(int argc, char** argv) {
     std::string data =
         argc - optind >= 3 ? argv[optind + 2] : std::string("null");
 
-    size_t colon = server.rfind(':');
     ZkConfig cfg;
-    cfg.host = colon == std::string::npos ? server
-                                          : server.substr(0, colon);
-    cfg.port = colon == std::string::npos
-                   ? 2181
-                   : (uint16_t)atoi(server.c_str() + colon + 1);
+    std::string listErr;
+    if (!parseHostList(server, defaultPort, cfg.servers, listErr)) {
+        fprintf(stderr, "zktool: %s\n", listErr.c_str());
+        return 1;
+    }
+    cfg.host = cfg.servers[0].host;
+    cfg.port = cfg.servers[0].port;
     cfg.sessionTimeoutMs = 10000;
 
     Ctx ctx;
