@@ -32,11 +32,22 @@ PY_EXT_SUFFIX := $(shell $(PYTHON)-config --extension-suffix 2>/dev/null || echo
 PY_INCLUDES := $(shell $(PYTHON) -m pybind11 --includes)
 PYMOD := binder_amd/_native$(PY_EXT_SUFFIX)
 
+# GPU batch resolver (native/gpu): HIP for gfx950, built wherever hipcc
+# is found; a box without it builds everything else as before.
+HIPCC ?= $(or $(shell command -v hipcc 2>/dev/null),$(wildcard /opt/rocm/bin/hipcc))
+HIP_ARCH ?= gfx950
+HIPFLAGS ?= -O2 -g0 -std=c++20 -fPIC -Wall -Wextra -Werror \
+	-Wno-unused-parameter -Xclang -target-feature -Xclang -packed-fp32-ops
+GPUMOD := binder_amd/_gpuresolve$(PY_EXT_SUFFIX)
+ifneq ($(and $(HIPCC),$(shell command -v $(HIPCC) 2>/dev/null)),)
+GPU_TARGETS := $(GPUMOD)
+endif
+
 BINARIES := bin/binderd bin/binder-balancer bin/dnsblast bin/bsockblast \
 	bin/binder-adjust bin/binder-supervisor bin/zklogcat bin/zktool \
 	bin/zkd
 
-all: $(PYMOD) $(BINARIES)
+all: $(PYMOD) $(BINARIES) $(GPU_TARGETS)
 
 bin/binderd: $(CORE_OBJS) $(SERVER_OBJS) $(BUILD)/native/server/binderd_main.o
 	@mkdir -p bin
@@ -86,6 +97,12 @@ $(BUILD)/native/pybind/module.o: native/pybind/module.cpp
 
 $(PYMOD): $(CORE_OBJS) $(BUILD)/native/pybind/module.o
 	$(CXX) -shared $(CXXFLAGS) $^ -o $@ $(LDFLAGS)
+
+# kernels, launcher and binding in one hipcc run; links amdhip64 only
+GPU_SRCS := native/gpu/resolve.cpp native/gpu/pymodule.cpp
+$(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp
+	$(HIPCC) -x hip --offload-arch=$(HIP_ARCH) $(HIPFLAGS) -Wno-error \
+	    $(PY_INCLUDES) -shared $(GPU_SRCS) -o $@
 
 # `make test` parity with the reference's nodeunit target
 # (Makefile:169-171 there)
@@ -270,14 +287,15 @@ release: all
 	cp -r tools dist/binder-amd/
 	cp etc/config.json.in etc/config.sample.json dist/binder-amd/etc/
 	mkdir -p dist/binder-amd/lib/python/binder_amd
-	cp binder_amd/*.py $(PYMOD) dist/binder-amd/lib/python/binder_amd/
+	cp binder_amd/*.py $(PYMOD) $(GPU_TARGETS) \
+	    dist/binder-amd/lib/python/binder_amd/
 	cp README.md LICENSE dist/binder-amd/
 	cp -r docs dist/binder-amd/
 	tar -C dist -czf dist/binder-amd.tar.gz binder-amd
 	@echo "release: dist/binder-amd.tar.gz"
 
 clean:
-	rm -rf $(BUILD) $(PYMOD) $(BINARIES) dist
+	rm -rf $(BUILD) $(PYMOD) $(GPUMOD) $(BINARIES) dist
 
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 

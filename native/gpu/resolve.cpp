@@ -1,0 +1,385 @@
+/*
+ * binder-amd: GPU batch resolver - the two gfx950 kernels.
+ *
+ * The CPU hit path (server.cpp: parseFast, answerHash, AnswerTable::
+ * find, serveHit) done for a whole run of queries at once. Lookups are
+ * independent reads of a static table, so one lane takes one query;
+ * replies are short byte strings at arbitrary alignment on both ends,
+ * so a 16-lane group takes one reply.
+ *
+ * Data movement of the lookup: a workgroup's kTile queries are one
+ * contiguous span of qbuf, fetched into LDS once with 16-byte loads
+ * (head and tail peeled bytewise, nothing outside the span is read).
+ * Parsing, hashing and the key compare then read the query from LDS
+ * bytewise. The dotted key is never materialised: key byte k is wire
+ * byte 13 + k, except that an inner length byte reads as '.' (see
+ * KeyReader). Slots are read one 16-byte load per probe step.
+ *
+ * Neither kernel trusts qoff: a tile or query whose offsets are not
+ * ascending inside qbuf is left unserved. Both trust the image, which
+ * the host has verified (answerimage.hpp).
+ */
+#include "resolve.hpp"
+
+#include <hip/hip_runtime.h>
+
+namespace bamd::gpu {
+
+namespace {
+
+constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kLenMul = 0xD6E8FEB86659FD93ull;
+constexpr uint64_t kStepMul = 0xBF58476D1CE4E5B9ull;
+constexpr uint64_t kSmMul2 = 0x94D049BB133111EBull;
+
+/* Streams the dotted key out of the wire name. `pos` is the wire
+ * position of the next key byte, `nextLen` the position of the next
+ * length byte; that byte reads as '.', and its value says where the
+ * one after it lies. */
+struct KeyReader {
+    const uint8_t* q;
+    uint32_t pos;
+    uint32_t nextLen;
+
+    __device__ __forceinline__ uint32_t next() {
+        uint32_t c = q[pos];
+        if (pos == nextLen) {
+            nextLen += c + 1;
+            c = '.';
+        }
+        ++pos;
+        return c;
+    }
+    __device__ __forceinline__ uint64_t word(uint32_t nbytes) {
+        uint32_t lo = 0, hi = 0;
+        for (uint32_t b = 0; b < nbytes && b < 4; ++b)
+            lo |= next() << (8 * b);
+        for (uint32_t b = 4; b < nbytes; ++b)
+            hi |= next() << (8 * (b - 4));
+        return ((uint64_t)hi << 32) | lo;
+    }
+};
+
+/* AnswerTable::hashKey, bit for bit, over the streamed key */
+__device__ __forceinline__ uint64_t hashKey(KeyReader r, uint32_t klen,
+                                            uint32_t qtype) {
+    uint64_t h = kGold ^ ((uint64_t)klen * kLenMul) ^
+                 ((uint64_t)qtype << 56);
+    uint32_t n = klen;
+    while (n >= 8) {
+        h = (h ^ r.word(8)) * kStepMul;
+        h ^= h >> 32;
+        n -= 8;
+    }
+    if (n != 0) {
+        h = (h ^ r.word(n)) * kStepMul;
+        h ^= h >> 32;
+    }
+    h ^= h >> 32;
+    h *= kGold;
+    h ^= h >> 29;
+    h *= kStepMul;
+    h ^= h >> 32;
+    return h;
+}
+
+/* One query: parseFastQuery()'s accept/reject decisions, then the
+ * table walk of AnswerTable::find(). Leaves *bodyOff / *total alone
+ * when the query is not served. */
+__device__ __forceinline__ void resolveOne(
+    const uint8_t* q, uint32_t len, const uint4* slots, uint32_t cap,
+    const uint8_t* arena, uint32_t* bodyOff, int32_t* total) {
+    if (len < 17 || len > (uint32_t)kMaxQuery) return;
+    /* flags: QR/opcode/AA/TC clear, RD free; byte 3 must be zero */
+    if (((q[2] & 0xFE) | q[3]) != 0) return;
+    /* counts: qd=1, an=ns=ar=0 */
+    if ((q[4] | (q[5] ^ 1) | q[6] | q[7] | q[8] | q[9] | q[10] |
+         q[11]) != 0)
+        return;
+
+    /* pass 1: walk the labels. nlen is the dotted name's length, p3
+     * the position of the third label's length byte, srvOk whether the
+     * first two labels are '_' followed by no further '_'. */
+    uint32_t pos = 12, nlen = 0, nlab = 0, p3 = 0;
+    bool srvOk = true;
+    while (true) {
+        if (pos >= len) return;
+        uint32_t l = q[pos++];
+        if (l == 0) break;
+        if ((l & 0xC0) != 0 || pos + l > len) return;
+        if (nlen + l + 1 > 256) return;
+        if (nlen > 0) ++nlen;
+        if (nlab == 2) p3 = pos - 1;
+        for (uint32_t k = 0; k < l; ++k) {
+            uint32_t c = q[pos + k];
+            bool ok = (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') ||
+                      c == '_' || c == '-';
+            if (!ok) return;
+            if (nlab < 2) srvOk &= (c == '_') == (k == 0);
+        }
+        nlen += l;
+        pos += l;
+        ++nlab;
+    }
+    if (pos + 4 > len) return;
+    uint32_t qtype = q[pos + 1];
+    if (q[pos] != 0 || (qtype != 1 && qtype != 33)) return;
+    if (q[pos + 2] != 0 || q[pos + 3] != 1) return;  /* class IN */
+
+    /* pass 2: hash. A: the whole name. SRV: from the third label on. */
+    KeyReader whole{q, 13, 13u + q[12]};
+    KeyReader hashed = whole;
+    uint32_t klen = nlen;
+    if (qtype == 33) {
+        if (nlab < 3 || !srvOk) return;
+        hashed = KeyReader{q, p3 + 1, p3 + 1 + q[p3]};
+        klen = nlen - (p3 - 12);
+    }
+    uint64_t h = hashKey(hashed, klen, qtype);
+    uint32_t hlo = (uint32_t)h, hhi = (uint32_t)(h >> 32);
+
+    /* probe: at most cap steps whatever the slots hold */
+    uint32_t mask = cap - 1;
+    uint32_t idx = hlo & mask;
+    for (uint32_t step = 0; step < cap; ++step, idx = (idx + 1) & mask) {
+        uint4 s = slots[idx];  /* hash lo, hash hi, off, len */
+        if (s.w == 0) return;
+        if (s.x != hlo || s.y != hhi) continue;
+        /* same hash: confirm klen, qtype and the whole name. nlen may
+         * be 256, which no blob's one-byte klen equals. */
+        const uint8_t* b = arena + s.z;
+        if (b[0] != nlen || b[1] != qtype) continue;
+        KeyReader r = whole;
+        bool same = true;
+        for (uint32_t k = 0; k < nlen; ++k) {
+            if (b[2 + k] != r.next()) {
+                same = false;
+                break;
+            }
+        }
+        if (!same) continue;
+        const uint8_t* body = b + 2 + nlen;
+        *bodyOff = s.z + 2 + nlen;
+        *total = (int32_t)(body[2] | ((uint32_t)body[3] << 8));
+        return;
+    }
+}
+
+/* Copy nbytes from src to dst, where dst - src is a multiple of 16
+ * (dst is in LDS): 16-byte loads over the aligned middle, bytes at
+ * both ends, nothing outside [src, src + nbytes) read. */
+__device__ __forceinline__ void loadSpan(uint8_t* dst, const uint8_t* src,
+                                         uint32_t nbytes) {
+    uint32_t tid = threadIdx.x;
+    uint32_t head = (16u - ((uint32_t)(uintptr_t)src & 15u)) & 15u;
+    if (head > nbytes) head = nbytes;
+    for (uint32_t k = tid; k < head; k += kTile) dst[k] = src[k];
+    uint32_t mid = (nbytes - head) / 16;
+    const uint4* s4 = (const uint4*)(src + head);
+    uint4* d4 = (uint4*)(dst + head);
+    for (uint32_t k = tid; k < mid; k += kTile) d4[k] = s4[k];
+    for (uint32_t k = head + mid * 16 + tid; k < nbytes; k += kTile)
+        dst[k] = src[k];
+}
+
+/* kGroup lanes copy n bytes, both ends at any alignment: bytes up to
+ * dst's dword boundary, whole dwords to the aligned middle of dst
+ * (from two aligned source dwords when src sits off by `sh` bytes),
+ * bytes for the rest. Reads at most 3 bytes before src, which the
+ * callers keep inside the blob, and none past src + n. */
+__device__ __forceinline__ void groupCopy(uint8_t* d, const uint8_t* s,
+                                          uint32_t n, uint32_t lane) {
+    uint32_t head = (uint32_t)(-(intptr_t)d) & 3u;
+    if (head > n) head = n;
+    if (lane < head) d[lane] = s[lane];
+    d += head;
+    s += head;
+    n -= head;
+    uint32_t m = n >> 2;
+    uint32_t sh = (uint32_t)(uintptr_t)s & 3u;
+    /* the last shifted dword would read 4 - sh bytes past its own end:
+     * leave it to the tail when the source does not have them */
+    if (sh != 0 && m != 0 && (n & 3u) < 4u - sh) --m;
+    uint32_t* d4 = (uint32_t*)d;
+    if (sh == 0) {
+        const uint32_t* s4 = (const uint32_t*)s;
+        for (uint32_t j = lane; j < m; j += kGroup) d4[j] = s4[j];
+    } else {
+        const uint32_t* s4 = (const uint32_t*)(s - sh);
+        uint32_t r = 8 * sh;
+        for (uint32_t j = lane; j < m; j += kGroup)
+            d4[j] = (s4[j] >> r) | (s4[j + 1] << (32 - r));
+    }
+    uint32_t done = 4 * m;  /* n - done < 8 */
+    if (lane < n - done) d[done + lane] = s[done + lane];
+}
+
+__device__ __forceinline__ uint32_t get16(const uint8_t* p) {
+    return p[0] | ((uint32_t)p[1] << 8);
+}
+
+__device__ __forceinline__ uint64_t splitmix(uint64_t x) {
+    x += kGold;
+    uint64_t z = (x ^ (x >> 30)) * kStepMul;
+    z = (z ^ (z >> 27)) * kSmMul2;
+    return z ^ (z >> 31);
+}
+
+/* head + 64 first segments + 64 second segments */
+constexpr int kMaxJobs = 129;
+
+/* One copy of a service reply: `src` counts from the body's start,
+ * `dst` from the reply's. */
+struct Job {
+    uint16_t src, dst, len;
+};
+
+/* Lane 0 of a group: draw the member order (Fisher-Yates from the
+ * counter-based generator) and lay out answerbody::serviceAssemble's
+ * copies - head, first segments in order, second segments in order.
+ * The head's first 12 bytes are left to the header patch. */
+__device__ void planService(const uint8_t* body, uint64_t seed,
+                            uint64_t index, uint8_t* order, Job* jobs) {
+    uint32_t n = body[1];
+    uint32_t headLen = get16(body + 4);
+    const uint8_t* tab = body + 6;
+    uint32_t headOff = 6 + 8 * n;
+    uint32_t segOff = headOff + headLen;
+    for (uint32_t i = 0; i < n; ++i) order[i] = (uint8_t)i;
+    uint64_t s0 = seed ^ (index * kLenMul);
+    uint64_t k = 0;
+    for (uint32_t i = n; i > 1;) {
+        --i;
+        uint64_t draw = splitmix(s0 + k * kGold);
+        uint32_t j = (uint32_t)(draw >> 32) % (i + 1);
+        uint8_t t = order[i];
+        order[i] = order[j];
+        order[j] = t;
+        ++k;
+    }
+    jobs[0] = Job{(uint16_t)(headOff + 12), 12, (uint16_t)(headLen - 12)};
+    uint32_t w = headLen;
+    for (uint32_t pass = 0; pass < 2; ++pass) {
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint8_t* e = tab + 8 * order[i] + 4 * pass;
+            uint32_t len = get16(e + 2);
+            jobs[1 + pass * n + i] = Job{(uint16_t)(segOff + get16(e)),
+                                         (uint16_t)w, (uint16_t)len};
+            w += len;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(kTile) void bamd_resolve_lookup(
+    const uint8_t* __restrict__ qbuf, const int32_t* __restrict__ qoff,
+    int64_t qbytes, int32_t n, const uint4* __restrict__ slots,
+    uint32_t cap, const uint8_t* __restrict__ arena,
+    uint32_t* __restrict__ bodyOff, int32_t* __restrict__ rlen) {
+    /* + 16: the span sits in LDS at its global address mod 16 */
+    __shared__ uint4 tile4[(kTileBytes + 16) / 16];
+    uint8_t* tile = (uint8_t*)tile4;
+
+    int32_t t0 = (int32_t)blockIdx.x * kTile;
+    int32_t t1 = t0 + kTile < n ? t0 + kTile : n;
+    int64_t b0 = qoff[t0], b1 = qoff[t1];
+    bool spanOk = b0 >= 0 && b1 >= b0 && b1 <= qbytes;
+    /* a span above kTileBytes holds a query above kMaxQuery: leave it
+     * in global memory, its lanes parse from there */
+    bool staged = spanOk && b1 - b0 <= kTileBytes;
+    uint32_t shift = 0;
+    if (staged) {
+        shift = (uint32_t)(uintptr_t)(qbuf + b0) & 15u;
+        loadSpan(tile + shift, qbuf + b0, (uint32_t)(b1 - b0));
+    }
+    __syncthreads();
+
+    int32_t i = t0 + (int32_t)threadIdx.x;
+    if (i >= t1) return;
+    int64_t o0 = qoff[i], o1 = qoff[i + 1];
+    uint32_t off = kUnserved;
+    int32_t total = 0;
+    if (cap != 0 && spanOk && o0 >= b0 && o1 >= o0 && o1 <= b1 &&
+        o1 - o0 <= kMaxQuery) {
+        uint32_t len = (uint32_t)(o1 - o0);
+        if (staged)
+            resolveOne(tile + shift + (uint32_t)(o0 - b0), len, slots, cap,
+                       arena, &off, &total);
+        else
+            resolveOne(qbuf + o0, len, slots, cap, arena, &off, &total);
+    }
+    bodyOff[i] = off;
+    rlen[i] = total;
+}
+
+extern "C" __global__ __launch_bounds__(kEmitBlock) void bamd_resolve_emit(
+    const uint8_t* __restrict__ qbuf, const int32_t* __restrict__ qoff,
+    int32_t n, const uint8_t* __restrict__ arena,
+    const uint32_t* __restrict__ bodyOff, const int32_t* __restrict__ rlen,
+    const int64_t* __restrict__ roff, uint8_t* __restrict__ rbuf,
+    uint64_t seed) {
+    __shared__ uint8_t order[kGroupsPerBlock][64];
+    __shared__ Job jobs[kGroupsPerBlock][kMaxJobs];
+
+    uint32_t g = threadIdx.x / kGroup, lane = threadIdx.x % kGroup;
+    int64_t i = (int64_t)blockIdx.x * kGroupsPerBlock + g;
+    uint32_t total = i < n ? (uint32_t)rlen[i] : 0;
+    const uint8_t* body = nullptr;
+    bool service = false;
+    if (total != 0) {
+        body = arena + bodyOff[i];
+        service = body[0] == 1;
+        if (service && lane == 0)
+            planService(body, seed, (uint64_t)i, order[g], jobs[g]);
+    }
+    __syncthreads();  /* the plans are in LDS; no barrier below */
+    if (total == 0) return;
+
+    uint8_t* dst = rbuf + roff[i];
+    const uint8_t* q = qbuf + qoff[i];
+    /* the reply's header: id and RD come from the query */
+    const uint8_t* first = service ? body + 6 + 8 * body[1] : body + 4;
+    if (lane < 12) {
+        uint32_t v = first[lane];
+        if (lane < 2) v = q[lane];
+        if (lane == 2) v |= q[2] & 1u;
+        dst[lane] = (uint8_t)v;
+    }
+    if (!service) {
+        groupCopy(dst + 12, first + 12, total - 12, lane);
+        return;
+    }
+    uint32_t njobs = 1 + 2 * body[1];
+    for (uint32_t j = 0; j < njobs; ++j) {
+        Job jb = jobs[g][j];
+        groupCopy(dst + jb.dst, body + jb.src, jb.len, lane);
+    }
+}
+
+hipError_t launchLookup(const Batch& b, const Image& img,
+                        uint32_t* bodyOff, int32_t* rlen,
+                        hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    uint32_t blocks = ((uint32_t)b.n + kTile - 1) / kTile;
+    hipLaunchKernelGGL(bamd_resolve_lookup, dim3(blocks), dim3(kTile), 0,
+                       stream, b.qbuf, b.qoff, b.qbytes, b.n,
+                       (const uint4*)img.slots, img.cap, img.arena, bodyOff,
+                       rlen);
+    return hipGetLastError();
+}
+
+hipError_t launchEmit(const Batch& b, const Image& img,
+                      const uint32_t* bodyOff, const int32_t* rlen,
+                      const int64_t* roff, uint8_t* rbuf, uint64_t seed,
+                      hipStream_t stream) {
+    if (b.n <= 0) return hipSuccess;
+    uint32_t blocks =
+        ((uint32_t)b.n + kGroupsPerBlock - 1) / kGroupsPerBlock;
+    hipLaunchKernelGGL(bamd_resolve_emit, dim3(blocks), dim3(kEmitBlock), 0,
+                       stream, b.qbuf, b.qoff, b.n, img.arena, bodyOff, rlen,
+                       roff, rbuf, seed);
+    return hipGetLastError();
+}
+
+}  // namespace bamd::gpu

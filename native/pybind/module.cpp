@@ -13,6 +13,8 @@
 #include "../dns/codec.hpp"
 #include "../engine/engine.hpp"
 #include "../engine/store.hpp"
+#include "../gpu/answerimage.hpp"
+#include "../server/fastparse.hpp"
 #include "../zk/hostlist.hpp"
 
 namespace py = pybind11;
@@ -355,6 +357,76 @@ PYBIND11_MODULE(_native, m) {
               return out;
           },
           py::arg("text"), py::arg("default_port") = 2181);
+
+    /* the server's fast-path parser (server/fastparse.hpp) itself, the
+     * accept/reject reference of the GPU batch resolver's tests */
+    m.def("parse_fast", [](py::bytes wire) -> py::object {
+        std::string_view sv = std::string_view(wire);
+        FastQuery q;
+        if (!parseFastQuery((const uint8_t*)sv.data(), sv.size(), q))
+            return py::none();
+        return py::make_tuple(py::bytes(q.name, q.nlen), q.isSrv,
+                              (int)q.keyOff);
+    });
+
+    /* host image of an answer table for the GPU batch resolver
+     * (gpu/answerimage.hpp); slots() and arena() hand out a verified
+     * snapshot */
+    py::class_<gpu::AnswerImage>(m, "AnswerImage")
+        .def(py::init<>())
+        .def("add_reply",
+             [](gpu::AnswerImage& im, py::bytes qname, int qtype,
+                py::bytes reply) {
+                 try {
+                     im.addReply(std::string_view(qname), qtype,
+                                 std::string_view(reply));
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("qname"), py::arg("qtype"), py::arg("reply"))
+        .def("add_service",
+             [](gpu::AnswerImage& im, py::bytes qname, int qtype,
+                py::bytes head,
+                const std::vector<std::pair<py::bytes, py::bytes>>& mem) {
+                 std::vector<gpu::AnswerImage::Member> members;
+                 members.reserve(mem.size());
+                 for (const auto& [a, b] : mem)
+                     members.emplace_back(std::string_view(a),
+                                          std::string_view(b));
+                 try {
+                     im.addService(std::string_view(qname), qtype,
+                                   std::string_view(head), members);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("qname"), py::arg("qtype"), py::arg("head"),
+             py::arg("members"))
+        .def("home_slot",
+             [](const gpu::AnswerImage& im, py::bytes qname, int qtype) {
+                 try {
+                     return im.homeSlot(std::string_view(qname), qtype);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("qname"), py::arg("qtype"))
+        .def("slots",
+             [](const gpu::AnswerImage& im) {
+                 im.verify();
+                 const AnswerTable& t = im.table();
+                 return py::bytes((const char*)t.slotData(),
+                                  t.slots() * 16);
+             })
+        .def("arena",
+             [](const gpu::AnswerImage& im) {
+                 im.verify();
+                 const AnswerTable& t = im.table();
+                 return py::bytes((const char*)t.arenaData(),
+                                  t.arenaBytes());
+             })
+        .def("__len__", &gpu::AnswerImage::size);
 
     py::class_<PyStubEngine>(m, "StubEngine")
         .def(py::init<const std::string&, const std::string&, bool>(),

@@ -102,6 +102,12 @@ class AnswerTable {
     uint64_t rebuilds() const { return rebuilds_; }
     uint64_t clears() const { return clears_; }
 
+    /* Read-only view for a snapshot (the GPU image): slots() x 16
+     * bytes of { hash u64, off u32, len u32 }, and arenaBytes() of
+     * blobs. Good until the next mutating call. */
+    const void* slotData() const { return slots_.get(); }
+    const uint8_t* arenaData() const { return arena_.get(); }
+
     void prefetchSlot(uint64_t h) const {
         if (cap_ != 0) __builtin_prefetch(&slots_[h & (cap_ - 1)]);
     }

@@ -36,6 +36,7 @@
 #include "../common/loop.hpp"
 #include "../engine/engine.hpp"
 #include "answertab.hpp"
+#include "fastparse.hpp"
 #include "metrics.hpp"
 
 namespace bamd {
@@ -221,26 +222,8 @@ class DnsServer {
                   const ClientInfo& ci, ReplySink& out,
                   const ReplyTarget& target);
 
-    /* A query the fast path may serve: header and question checked,
-     * name lowercase [a-z0-9_-] labels in dotted form. For SRV the
-     * store key is the name behind the _svc._proto labels. */
-    struct FastQuery {
-        char name[256];
-        uint16_t nlen = 0;
-        uint16_t keyOff = 0;  /* SRV: where the service's domain starts */
-        uint16_t svcLen = 0;  /* SRV: length of the _svc label */
-        bool isSrv = false;
-        uint64_t hash = 0;    /* answer-table hash, see answerHash() */
-
-        std::string_view qname() const { return {name, nlen}; }
-        std::string_view key() const {
-            return {name + keyOff, (size_t)(nlen - keyOff)};
-        }
-        std::string_view svc() const { return {name, svcLen}; }
-        std::string_view proto() const {
-            return {name + svcLen + 1, (size_t)(keyOff - svcLen - 2)};
-        }
-    };
+    /* the fast path's parser lives in fastparse.hpp */
+    using FastQuery = bamd::FastQuery;
     static bool parseFast(const uint8_t* data, size_t len, FastQuery& q);
     /* policy checks + store lookup + cached-record serve (the fast
      * path proper); memoises what it served when `memo` is set */

@@ -1,0 +1,215 @@
+#!/usr/bin/env python3
+"""Time the GPU batch resolver (binder_amd.gpuresolve) and record the
+result in profiles/GPURESOLVE.md.
+
+Workload: 1 000 000 queries, 90 % A and 10 % SRV, against the bench.py
+tree's shape: 10 000 hosts plus 100 services of 8 members (each service
+has its A and its SRV entry). Device events around resolve() and around
+each kernel on buffers allocated beforehand; warm-up first; median and
+min..max of the repeats. Bytes per query are the bytes the algorithm
+has to move, computed from the shapes, not counters.
+
+The measurement runs in one child process under a time limit. Without a
+GPU or the extension the file says "not measured".
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import random
+import statistics
+import struct
+import subprocess
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO))
+OUT = REPO / "profiles" / "GPURESOLVE.md"
+HOSTS, SERVICES, MEMBERS = 10_000, 100, 8
+
+
+def labels(name: bytes) -> bytes:
+    return b"".join(bytes([len(p)]) + p for p in name.split(b".")) + b"\0"
+
+
+def query(name: bytes, qtype: int) -> bytes:
+    return (struct.pack(">HHHHHH", 0x4242, 0x0100, 1, 0, 0, 0) +
+            labels(name) + struct.pack(">HH", qtype, 1))
+
+
+def header(name: bytes, qtype: int, an: int, ar: int) -> bytes:
+    return (struct.pack(">HHHHHH", 0, 0x8400, 1, an, 0, ar) +
+            labels(name) + struct.pack(">HH", qtype, 1))
+
+
+def rr(owner: bytes, rtype: int, rdata: bytes) -> bytes:
+    return owner + struct.pack(">HHIH", rtype, 1, 30, len(rdata)) + rdata
+
+
+def build_image(native):
+    """The table, the distinct queries, and (klen, body bytes read,
+    reply bytes) per distinct query for the byte counts."""
+    image, a_q, srv_q = native.AnswerImage(), [], []
+    ptr = b"\xc0\x0c"
+    for i in range(HOSTS):
+        name = b"h%d.bench.foo.com" % i
+        reply = header(name, 1, 1, 0) + rr(ptr, 1, bytes([10, 0, i >> 8,
+                                                          i & 255]))
+        image.add_reply(name, 1, reply)
+        a_q.append((query(name, 1), len(name), 4 + len(reply), len(reply)))
+    for s in range(SERVICES):
+        dom = b"svc%d.bench.foo.com" % s
+        srv = b"_http._tcp." + dom
+        mem_a, mem_srv = [], []
+        for m in range(MEMBERS):
+            addr = bytes([10, 1, s, m])
+            # short member names: the 8-member SRV reply must fit 512
+            target = labels(b"m%d-s%d" % (m, s))
+            mem_a.append((rr(ptr, 1, addr), b""))
+            mem_srv.append((rr(ptr, 33, struct.pack(">HHH", 0, 10, 80) +
+                               target), rr(target, 1, addr)))
+        for name, qt, head, mem, qs in (
+                (dom, 1, header(dom, 1, MEMBERS, 0), mem_a, a_q),
+                (srv, 33, header(srv, 33, MEMBERS, MEMBERS), mem_srv,
+                 srv_q)):
+            image.add_service(name, qt, head, mem)
+            total = len(head) + sum(len(a) + len(b) for a, b in mem)
+            qs.append((query(name, qt), len(name), 6 + 8 * MEMBERS + total,
+                       total))
+    return image, a_q, srv_q
+
+
+def worker(n: int, repeats: int) -> dict:
+    import torch
+    from binder_amd import _gpuresolve, _native, gpuresolve
+
+    image, a_q, srv_q = build_image(_native)
+    rng = random.Random(1)
+    picks = [rng.choice(srv_q) if rng.random() < 0.1 else rng.choice(a_q)
+             for _ in range(n)]
+    offs = [0]
+    for p in picks:
+        offs.append(offs[-1] + len(p[0]))
+    # the bytes the two kernels must move, per query: query + its offset +
+    # one slot + blob key and body head in; 8 bytes of result out; then
+    # result, offsets and 3 query bytes + the body in; the reply out
+    look_rd = sum(len(q) + 4 + 16 + 2 + klen + 4 for q, klen, _, _ in picks)
+    emit_rd = sum(4 + 4 + 8 + 4 + 3 + body for _, _, body, _ in picks)
+    emit_wr = sum(total for _, _, _, total in picks)
+    qbuf_h = torch.frombuffer(bytearray(b"".join(p[0] for p in picks)),
+                              dtype=torch.uint8).pin_memory()
+    qoff_h = torch.tensor(offs, dtype=torch.int32).pin_memory()
+    table = gpuresolve.GpuAnswerTable(image)
+
+    def timed(fn):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        out = fn()
+        ev[1].record()
+        ev[1].synchronize()
+        return ev[0].elapsed_time(ev[1]), out
+
+    def series(fn):
+        for _ in range(3):
+            timed(fn)
+        ms = sorted(timed(fn)[0] for _ in range(repeats))
+        return {"median_ms": statistics.median(ms), "min_ms": ms[0],
+                "max_ms": ms[-1]}
+
+    res = {"n": n, "repeats": repeats, "tile": gpuresolve.TILE,
+           "group": gpuresolve.GROUP, "device": torch.cuda.get_device_name(),
+           "entries": len(image), "slots": table.cap}
+    res["upload"] = series(lambda: (qbuf_h.to("cuda", non_blocking=True),
+                                    qoff_h.to("cuda", non_blocking=True)))
+    qbuf, qoff = qbuf_h.cuda(), qoff_h.cuda()
+    res["resolve"] = series(lambda: table.resolve(qbuf, qoff, seed=7))
+    rbuf, roff = table.resolve(qbuf, qoff, seed=7)
+    assert int(roff[-1]) == emit_wr and bool((roff[1:] > roff[:-1]).all())
+    res["download"] = series(lambda: rbuf.cpu())
+
+    stream = torch.cuda.current_stream().cuda_stream
+    body_off = torch.empty(n, dtype=torch.int32, device="cuda")
+    rlen = torch.empty(n, dtype=torch.int32, device="cuda")
+    batch = (qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n)
+    res["lookup"] = series(lambda: _gpuresolve.lookup(
+        *batch, table._slots.data_ptr(), table.cap, table._arena.data_ptr(),
+        body_off.data_ptr(), rlen.data_ptr(), stream))
+    res["emit"] = series(lambda: _gpuresolve.emit(
+        *batch, table._arena.data_ptr(), body_off.data_ptr(),
+        rlen.data_ptr(), roff.data_ptr(), rbuf.data_ptr(), 7, stream))
+    kernel_s = (res["lookup"]["median_ms"] + res["emit"]["median_ms"]) / 1e3
+    res["bytes_per_query"] = {"lookup_read": look_rd / n, "lookup_write": 8.0,
+                              "emit_read": emit_rd / n,
+                              "emit_write": emit_wr / n}
+    res["kernel_qps"] = n / kernel_s
+    res["kernel_gbps"] = (look_rd + 8 * n + emit_rd + emit_wr) / kernel_s / 1e9
+    res["resolve_qps"] = n / (res["resolve"]["median_ms"] / 1e3)
+    return res
+
+
+CONTEXT = """
+Context only: the CPU hit path costs about 100-125 ns per query per core
+(`profiles/SCALING.md`). That figure comes from a different box and
+round; no ratio is claimed from it.
+"""
+
+
+def render(res) -> str:
+    head = "# GPU batch resolver: timing\n\n"
+    if res is None:
+        return head + "not measured\n" + CONTEXT
+
+    def row(name, key):
+        s = res[key]
+        return (f"| {name} | {s['median_ms']:.3f} | {s['min_ms']:.3f} .. "
+                f"{s['max_ms']:.3f} |\n")
+    b = res["bytes_per_query"]
+    return (head + f"`scripts/gpuresolve_bench.py` on {res['device']}: "
+            f"{res['n']} queries (90 % A, 10 % SRV), {res['entries']} "
+            f"entries in {res['slots']} slots, {res['repeats']} repeats "
+            "after warm-up, device events.\n\n"
+            f"Choices: T = {res['tile']} queries per lookup workgroup, "
+            f"{res['group']} lanes per reply in emit.\n\n"
+            "| step | median ms | min .. max ms |\n|---|---|---|\n" +
+            row("upload qbuf + qoff (pinned)", "upload") +
+            row("resolve() whole", "resolve") +
+            row("bamd_resolve_lookup", "lookup") +
+            row("bamd_resolve_emit", "emit") +
+            row("download rbuf", "download") +
+            f"\n- kernels: {res['kernel_qps'] / 1e6:.1f} M queries/s, "
+            f"{res['kernel_gbps']:.1f} GB/s of needed bytes over kernel "
+            "time\n"
+            f"- resolve() whole: {res['resolve_qps'] / 1e6:.1f} M queries/s "
+            "(adds the prefix sum, allocations and one synchronise)\n"
+            f"- bytes per query from the shapes: lookup reads "
+            f"{b['lookup_read']:.1f} and writes {b['lookup_write']:.0f}; "
+            f"emit reads {b['emit_read']:.1f} and writes "
+            f"{b['emit_write']:.1f}\n" + CONTEXT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--repeats", type=int, default=25)
+    ap.add_argument("--timeout", type=int, default=300)
+    ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--out", type=Path, default=OUT)
+    args = ap.parse_args()
+    if args.worker:
+        print(json.dumps(worker(args.n, max(20, args.repeats))))
+        return 0
+    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable,
+           __file__, "--worker", "--n", str(args.n), "--repeats",
+           str(args.repeats)]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    res = json.loads(p.stdout.splitlines()[-1]) if p.returncode == 0 else None
+    if res is None:
+        print(p.stderr[-2000:], file=sys.stderr)
+    args.out.write_text(render(res))
+    print(render(res))
+    return 0 if res is not None else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
