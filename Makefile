@@ -99,8 +99,10 @@ $(PYMOD): $(CORE_OBJS) $(BUILD)/native/pybind/module.o
 	$(CXX) -shared $(CXXFLAGS) $^ -o $@ $(LDFLAGS)
 
 # kernels, launcher and binding in one hipcc run; links amdhip64 only
-GPU_SRCS := native/gpu/resolve.cpp native/gpu/pymodule.cpp
-$(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp
+GPU_SRCS := native/gpu/resolve.cpp native/gpu/update.cpp \
+	native/gpu/pymodule.cpp
+$(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp native/gpu/update.hpp \
+		native/gpu/devcopy.hpp
 	$(HIPCC) -x hip --offload-arch=$(HIP_ARCH) $(HIPFLAGS) -Wno-error \
 	    $(PY_INCLUDES) -shared $(GPU_SRCS) -o $@
 
@@ -143,6 +145,22 @@ $(BUILD)/answertab_check: native/server/answertab_check_main.cpp \
 
 check-answertab: $(BUILD)/answertab_check
 	$(BUILD)/answertab_check 1 100000
+
+# Sanitizer run of the GPU resolver's update batch (gpu/answerdelta.hpp)
+# in a stand-alone program: seeded random upserts and invalidations; the
+# packed normal form applied in its two phases to a std::map must equal
+# the same calls applied one by one, and every packed blob is verified
+# again. Host-only, CPU-only.
+$(BUILD)/answerdelta_check: native/gpu/answerdelta_check_main.cpp \
+		native/gpu/answerdelta.hpp native/gpu/answerrules.hpp \
+		native/server/answertab.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-answerdelta: $(BUILD)/answerdelta_check
+	$(BUILD)/answerdelta_check 1 300
 
 # Sanitizer run of the balancer's reply-run grouping (replyruns.hpp) in a
 # stand-alone program with a recording sink: fixed and seeded random
@@ -300,5 +318,6 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
+	check-answerdelta \
 	check-replyruns check-shmpipe check-bsocklink check-serve-threads \
 	check-codec check-wire-asan check-zkhosts release

@@ -1,15 +1,20 @@
-"""GPU batch resolver: a whole run of wire queries against a static
-answer image, on the MI355X.
+"""GPU batch resolver: a whole run of wire queries against an answer
+table in device memory, on the MI355X.
 
     image = _native.AnswerImage()        # filled on the host, verified
     table = GpuAnswerTable(image)        # uploaded once
     rbuf, roff = table.resolve(qbuf, qoff)
+    delta = _native.AnswerDelta()        # invalidations and upserts
+    table.apply(delta)                   # in place, on the device
 
 The work is two hand-written gfx950 kernels (native/gpu/resolve.cpp):
 `bamd_resolve_lookup` parses, hashes and probes one query per lane,
 `bamd_resolve_emit` copies or assembles the replies into one packed
 buffer. torch is the plumbing only: it owns the buffers, the stream and
-the prefix sum between the two kernels. A query the image does not
+the prefix sum between the two kernels. The table follows the registry
+through apply(): four more kernels (native/gpu/update.cpp) tombstone
+what a delta invalidates, claim or replace slots for what it upserts,
+and compact the table when dead space has built up. A query the image does not
 answer gets an empty reply (`roff[i + 1] == roff[i]`); the caller sends
 it down the CPU path.
 
@@ -41,26 +46,167 @@ _native = require_native()
 TILE = _gpuresolve.TILE        # queries per lookup workgroup
 GROUP = _gpuresolve.GROUP      # lanes per reply in emit
 MAX_QUERY = _gpuresolve.MAX_QUERY
+OP_BLOCK = _gpuresolve.OP_BLOCK  # ops per update workgroup
+
+
+def _pow2(n):
+    return 1 << max(0, int(n) - 1).bit_length()
 
 
 class GpuAnswerTable:
-    """A static snapshot of an AnswerImage in device memory."""
+    """An AnswerImage in device memory, kept current with apply().
 
-    def __init__(self, image, device="cuda"):
+    Everything runs on the current stream: a resolve() after an apply()
+    on the same stream sees the whole delta. apply(), compact() and
+    resolve() are not safe concurrently on different streams."""
+
+    MIN_SLOTS = 1024
+    MIN_ARENA = 4096
+    MAX_ARENA = 2 ** 32 - 16  # slot offsets are 32 bits
+
+    def __init__(self, image, device="cuda", reserve_entries=0,
+                 reserve_bytes=0):
         if not isinstance(image, _native.AnswerImage):
             raise TypeError("GpuAnswerTable takes an _native.AnswerImage")
         self.device = torch.device(device)
         slots, arena = image.slots(), image.arena()  # verified copies
         self.cap = len(slots) // 16
-        self.entries = len(image)
+        self.entries = len(image)  # exact as of the last compaction
         self._slots = self._upload(slots)
-        self._arena = self._upload(arena)
+        # the tombstone blob, two zero bytes, lies behind the arena
+        self._used = len(arena)
+        self._arena_cap = max(self._used, reserve_bytes)
+        self._arena = torch.zeros(self._arena_cap + 2, dtype=torch.uint8,
+                                  device=self.device)
+        self._arena[:self._used].copy_(self._upload(arena))
+        self._occ = self.entries    # upper bound: live + tombstones
+        self._counters = torch.zeros(_gpuresolve.COUNTERS,
+                                     dtype=torch.int32, device=self.device)
+        self._seen = torch.zeros(_gpuresolve.COUNTERS,
+                                 dtype=torch.int32).pin_memory()
+        self._seen_event = None     # (event, used) of a read in flight
+        self._last = ([0] * _gpuresolve.COUNTERS, self._used)
+        self.compactions = 0
+        want_slots = _pow2(2 * reserve_entries) if reserve_entries else 0
+        if want_slots > self.cap:
+            with torch.cuda.device(self.device):
+                self._rebuild(min_slots=want_slots,
+                              min_bytes=self._arena_cap)
+            self.compactions = 0
 
     def _upload(self, data: bytes):
         if not data:
             return torch.empty(0, dtype=torch.uint8, device=self.device)
         host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
         return host.to(self.device)
+
+    def _table(self):
+        return (self._slots.data_ptr(), self.cap, self._arena.data_ptr(),
+                self._arena_cap, self._counters.data_ptr())
+
+    def _rebuild(self, extra_entries=0, extra_bytes=0, min_slots=0,
+                 min_bytes=0):
+        """Compact into fresh buffers with room for a batch of
+        extra_entries blobs of extra_bytes: scan, torch's prefix sum,
+        move. Reads the exact live counts back (one synchronise)."""
+        dev = self.device
+        stream = torch.cuda.current_stream().cuda_stream
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        lens = torch.empty(self.cap, dtype=torch.int32, device=dev)
+        _gpuresolve.scan(self._slots.data_ptr(), self.cap, lens.data_ptr(),
+                         totals.data_ptr(), stream)
+        incl = torch.cumsum(lens, 0, dtype=torch.int64)
+        live, live_bytes = totals.tolist()
+        ncap = _pow2(max(4 * (live + extra_entries), min_slots,
+                         self.MIN_SLOTS))
+        nbytes = max(2 * (live_bytes + extra_bytes), min_bytes,
+                     self.MIN_ARENA)
+        if nbytes > self.MAX_ARENA or ncap > 2 ** 31:
+            raise ValueError("answer table above 2^32 arena bytes")
+        nslots = torch.zeros(ncap * 16, dtype=torch.uint8, device=dev)
+        narena = torch.empty(nbytes + 2, dtype=torch.uint8, device=dev)
+        _gpuresolve.move(self._slots.data_ptr(), self.cap,
+                         self._arena.data_ptr(), lens.data_ptr(),
+                         incl.data_ptr(), nslots.data_ptr(), ncap,
+                         narena.data_ptr(), nbytes,
+                         self._counters.data_ptr(), stream)
+        self._slots, self.cap = nslots, ncap
+        self._arena, self._arena_cap = narena, nbytes
+        self._used, self._occ, self.entries = live_bytes, live, live
+        self.compactions += 1
+        self._seen_event = None
+        self._last = ([0] * _gpuresolve.COUNTERS, self._used)
+
+    def _crowded(self):
+        """Dead bytes above live bytes, or tombstones above live
+        entries, by the counters as the last finished apply() left
+        them; no wait."""
+        if self._seen_event is not None and self._seen_event[0].query():
+            used = self._seen_event[1]
+            self._last = ([c & 0xFFFFFFFF for c in self._seen.tolist()],
+                          used)
+            self._seen_event = None
+        (tombs, dead, claims, _), used = self._last
+        return dead > used - dead or tombs > self.entries + claims - tombs
+
+    def apply(self, delta):
+        """Apply an _native.AnswerDelta in place: all its invalidations,
+        then all its upserts, by HIP kernels on the current stream.
+        Makes room first (a compaction into larger buffers) when the
+        batch could load the slot array above 1/2 or overrun the arena,
+        and compacts when dead space has outgrown the live data. Not
+        safe concurrently with resolve() on another stream."""
+        if not isinstance(delta, _native.AnswerDelta):
+            raise TypeError("apply takes an _native.AnswerDelta")
+        p = delta.pack()
+        ni, nu = len(p["ioff"]) // 4 - 1, len(p["uoff"]) // 4 - 1
+        ibytes, ubytes = len(p["ibuf"]), len(p["ubuf"])
+        if ni + nu == 0:
+            return
+        with torch.cuda.device(self.device):
+            if 2 * (self._occ + nu) > self.cap or \
+                    self._used + ubytes > self._arena_cap or self._crowded():
+                self._rebuild(nu, ubytes)
+            stream = torch.cuda.current_stream().cuda_stream
+            # one upload: 8-byte hashes, 4-byte offsets, domain bytes
+            ops = self._upload(p["ihash"] + p["uhash"] + p["ioff"] +
+                               p["uoff"] + p["ibuf"])
+            ihash = ops.data_ptr()
+            uhash = ihash + 16 * ni
+            ioff = uhash + 8 * nu
+            uoff = ioff + 4 * (ni + 1)
+            ibuf = uoff + 4 * (nu + 1)
+            if ni:
+                _gpuresolve.invalidate(*self._table(), ibuf, ioff, ibytes,
+                                       ihash, ni, stream)
+            if nu:
+                # the blobs go into the arena as they are, end to end
+                self._arena[self._used:self._used + ubytes].copy_(
+                    torch.frombuffer(bytearray(p["ubuf"]),
+                                     dtype=torch.uint8))
+                _gpuresolve.insert(*self._table(), self._used, uoff, ubytes,
+                                   uhash, nu, stream)
+                self._used += ubytes
+                self._occ += nu
+            self._seen.copy_(self._counters, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            self._seen_event = (event, self._used)
+
+    def compact(self, min_slots=0):
+        """Rebuild slots and arena from the live entries on the device:
+        no tombstones, no dead bytes, at least min_slots slots."""
+        with torch.cuda.device(self.device):
+            self._rebuild(min_slots=min_slots)
+
+    def stats(self):
+        """Exact counts; one small device read."""
+        tombs, dead, claims, _ = (c & 0xFFFFFFFF
+                                  for c in self._counters.tolist())
+        return {"entries": self.entries + claims - tombs,
+                "slots": self.cap, "tombstones": tombs,
+                "arena_bytes": self._used, "dead_bytes": dead,
+                "compactions": self.compactions}
 
     def resolve(self, qbuf, qoff, seed=0):
         """qbuf: uint8 query bytes end to end; qoff: int32 [N + 1].

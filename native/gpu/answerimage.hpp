@@ -22,23 +22,16 @@
  */
 #pragma once
 
-#include <cstdint>
-#include <stdexcept>
-#include <string>
-#include <string_view>
-#include <utility>
-#include <vector>
-
-#include "../server/answertab.hpp"
+#include "answerrules.hpp"
 
 namespace bamd::gpu {
 
 class AnswerImage {
   public:
-    static constexpr size_t kMaxReply = 512;
-    static constexpr size_t kMinReply = 12;
+    static constexpr size_t kMaxReply = gpu::kMaxReply;
+    static constexpr size_t kMinReply = gpu::kMinReply;
 
-    using Member = std::pair<std::string_view, std::string_view>;
+    using Member = gpu::Member;
 
     size_t size() const { return tab_.size(); }
     const AnswerTable& table() const { return tab_; }
@@ -52,10 +45,7 @@ class AnswerImage {
     void addReply(std::string_view qname, int qtype,
                   std::string_view reply) {
         uint64_t h = hashOf(qname, qtype);
-        if (reply.size() < kMinReply)
-            throw std::invalid_argument("reply shorter than a header");
-        if (reply.size() > kMaxReply)
-            throw std::invalid_argument("reply longer than 512 bytes");
+        checkReply(reply);
         uint8_t* body = tab_.insert(
             h, (uint8_t)qtype, qname.data(), qname.size(),
             answerbody::wireBodyLen(reply.size()));
@@ -70,22 +60,9 @@ class AnswerImage {
                     const std::vector<Member>& members) {
         uint64_t h = hashOf(qname, qtype);
         size_t n = members.size();
-        if (n > answerbody::kMaxMembers)
-            throw std::invalid_argument("more than 64 members");
-        if (head.size() < kMinReply)
-            throw std::invalid_argument("head shorter than a header");
         answerbody::Seg s1[answerbody::kMaxMembers];
         answerbody::Seg s2[answerbody::kMaxMembers];
-        size_t segBytes = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const auto& [a, b] = members[i];
-            s1[i] = {(const uint8_t*)a.data(), a.size()};
-            s2[i] = {(const uint8_t*)b.data(), b.size()};
-            segBytes += a.size() + b.size();
-            if (segBytes > kMaxReply) break;
-        }
-        if (head.size() + segBytes > kMaxReply)
-            throw std::invalid_argument("reply longer than 512 bytes");
+        size_t segBytes = checkService(head, members, s1, s2);
         uint8_t* body = tab_.insert(
             h, (uint8_t)qtype, qname.data(), qname.size(),
             answerbody::serviceBodyLen(n, head.size(), segBytes));
@@ -101,8 +78,8 @@ class AnswerImage {
         size_t cap = tab_.slots(), used = tab_.arenaBytes();
         if (cap == 0) return;
         if ((cap & (cap - 1)) != 0 || cap > 0x80000000u)
-            fail("slot count is not a power of two below 2^32");
-        if (tab_.size() * 2 > cap) fail("load above 1/2");
+            imageFail("slot count is not a power of two below 2^32");
+        if (tab_.size() * 2 > cap) imageFail("load above 1/2");
         const SlotView* sl = (const SlotView*)tab_.slotData();
         const uint8_t* arena = tab_.arenaData();
         size_t live = 0;
@@ -110,10 +87,10 @@ class AnswerImage {
             if (sl[i].len == 0) continue;
             ++live;
             if ((size_t)sl[i].off + sl[i].len > used)
-                fail("blob outside the arena");
+                imageFail("blob outside the arena");
             verifyBlob(arena + sl[i].off, sl[i].len);
         }
-        if (live != tab_.size()) fail("slot count mismatch");
+        if (live != tab_.size()) imageFail("slot count mismatch");
     }
 
   private:
@@ -122,62 +99,6 @@ class AnswerImage {
         uint32_t off;
         uint32_t len;
     };
-
-    [[noreturn]] static void fail(const char* what) {
-        throw std::runtime_error(std::string("answer image: ") + what);
-    }
-
-    static void verifyBlob(const uint8_t* b, size_t len) {
-        using answerbody::get16;
-        if (len < 2 || len < 2 + (size_t)b[0] + 4) fail("short blob");
-        if (b[1] != 1 && b[1] != 33) fail("qtype not A or SRV");
-        const uint8_t* body = b + 2 + b[0];
-        size_t blen = len - 2 - b[0];
-        size_t total = answerbody::total(body);
-        if (total < kMinReply || total > kMaxReply) fail("bad total");
-        if (answerbody::kind(body) == answerbody::kWire) {
-            if (blen != answerbody::wireBodyLen(total))
-                fail("wire body length");
-            return;
-        }
-        if (answerbody::kind(body) != answerbody::kService)
-            fail("unknown body kind");
-        size_t n = body[1];
-        if (n > answerbody::kMaxMembers || blen < 6 + 8 * n)
-            fail("bad member count");
-        size_t headLen = get16(body + 4);
-        if (headLen < kMinReply || blen < 6 + 8 * n + headLen)
-            fail("bad head");
-        size_t segBytes = blen - 6 - 8 * n - headLen;
-        size_t sum = headLen;
-        for (size_t i = 0; i < 2 * n; ++i) {
-            const uint8_t* e = body + 6 + 4 * i;
-            if (get16(e) + get16(e + 2) > segBytes)
-                fail("segment outside the blob");
-            sum += get16(e + 2);
-        }
-        if (sum != total) fail("segments do not add up to total");
-    }
-
-    /* DnsServer::answerHash on a dotted name: A on the whole name, SRV
-     * on what follows the second label */
-    static uint64_t hashOf(std::string_view qname, int qtype) {
-        if (qtype != 1 && qtype != 33)
-            throw std::invalid_argument("qtype must be 1 (A) or 33 (SRV)");
-        if (qname.size() > AnswerTable::kMaxKey)
-            throw std::invalid_argument("key longer than 255 bytes");
-        if (qtype == 1)
-            return AnswerTable::hashKey(qname.data(), qname.size(), 1);
-        size_t d1 = qname.find('.');
-        size_t d2 = d1 == std::string_view::npos
-                        ? d1
-                        : qname.find('.', d1 + 1);
-        if (d2 == std::string_view::npos || d2 + 1 >= qname.size())
-            throw std::invalid_argument(
-                "SRV name is not _svc._proto.domain");
-        return AnswerTable::hashKey(qname.data() + d2 + 1,
-                                    qname.size() - d2 - 1, 33);
-    }
 
     AnswerTable tab_;
 };

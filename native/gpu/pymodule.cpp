@@ -10,6 +10,7 @@
 #include <string>
 
 #include "resolve.hpp"
+#include "update.hpp"
 
 namespace py = pybind11;
 using namespace bamd::gpu;
@@ -32,6 +33,24 @@ Batch batch(uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n) {
         throw std::invalid_argument("batch out of range");
     return Batch{ptr<const uint8_t>(qbuf), ptr<const int32_t>(qoff), qbytes,
                  (int32_t)n};
+}
+
+/* a table the update kernels may write: a power-of-two slot array and
+ * an arena below 2^32 bytes with its tombstone blob at `tomb` */
+Table table(uintptr_t slots, uint64_t cap, uintptr_t arena, uint64_t tomb,
+            uintptr_t counters) {
+    if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+        throw std::invalid_argument("cap not a power of two");
+    if (tomb > 0xFFFFFFFFu - kTombLen)
+        throw std::invalid_argument("arena above 2^32 bytes");
+    return Table{ptr<void>(slots), (uint32_t)cap, ptr<uint8_t>(arena),
+                 (uint32_t)tomb, ptr<uint32_t>(counters)};
+}
+
+int32_t count(int64_t v) {
+    if (v < 0 || v > 0x7FFFFFFF)
+        throw std::invalid_argument("op batch out of range");
+    return (int32_t)v;
 }
 
 }  // namespace
@@ -76,4 +95,73 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
           py::arg("roff"), py::arg("rbuf"), py::arg("seed"),
           py::arg("stream"));
+
+    m.attr("OP_BLOCK") = kOpBlock;
+    m.attr("COUNTERS") = (int)kCounters;
+
+    m.def("invalidate",
+          [](uintptr_t slots, uint64_t cap, uintptr_t arena, uint64_t tomb,
+             uintptr_t counters, uintptr_t ibuf, uintptr_t ioff,
+             int64_t ibytes, uintptr_t ihash, int64_t n,
+             uintptr_t stream) {
+              check(launchInvalidate(
+                        table(slots, cap, arena, tomb, counters),
+                        ptr<const uint8_t>(ibuf), ptr<const int32_t>(ioff),
+                        count(ibytes), ptr<const uint64_t>(ihash), count(n),
+                        ptr<ihipStream_t>(stream)),
+                    "bamd_update_invalidate");
+          },
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("tomb"), py::arg("counters"), py::arg("ibuf"),
+          py::arg("ioff"), py::arg("ibytes"), py::arg("ihash"),
+          py::arg("n"), py::arg("stream"));
+
+    m.def("insert",
+          [](uintptr_t slots, uint64_t cap, uintptr_t arena, uint64_t tomb,
+             uintptr_t counters, uint64_t used, uintptr_t uoff,
+             int64_t ubytes, uintptr_t uhash, int64_t n,
+             uintptr_t stream) {
+              if (used + (uint64_t)count(ubytes) > tomb)
+                  throw std::invalid_argument("batch outside the arena");
+              check(launchInsert(table(slots, cap, arena, tomb, counters),
+                                 (uint32_t)used, ptr<const int32_t>(uoff),
+                                 count(ubytes), ptr<const uint64_t>(uhash),
+                                 count(n), ptr<ihipStream_t>(stream)),
+                    "bamd_update_insert");
+          },
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("tomb"), py::arg("counters"), py::arg("used"),
+          py::arg("uoff"), py::arg("ubytes"), py::arg("uhash"),
+          py::arg("n"), py::arg("stream"));
+
+    m.def("scan",
+          [](uintptr_t slots, uint64_t cap, uintptr_t lens,
+             uintptr_t totals, uintptr_t stream) {
+              check(launchScan(table(slots, cap, 0, 0, 0),
+                               ptr<int32_t>(lens),
+                               ptr<unsigned long long>(totals),
+                               ptr<ihipStream_t>(stream)),
+                    "bamd_update_scan");
+          },
+          py::arg("slots"), py::arg("cap"), py::arg("lens"),
+          py::arg("totals"), py::arg("stream"));
+
+    m.def("move",
+          [](uintptr_t slots, uint64_t cap, uintptr_t arena, uintptr_t lens,
+             uintptr_t incl, uintptr_t nslots, uint64_t ncap,
+             uintptr_t narena, uint64_t ntomb, uintptr_t counters,
+             uintptr_t stream) {
+              if (ncap == 0)
+                  throw std::invalid_argument("no slots to move into");
+              check(launchMove(table(slots, cap, arena, 0, 0),
+                               ptr<const int32_t>(lens),
+                               ptr<const int64_t>(incl),
+                               table(nslots, ncap, narena, ntomb, counters),
+                               ptr<ihipStream_t>(stream)),
+                    "bamd_update_move");
+          },
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("lens"), py::arg("incl"), py::arg("nslots"),
+          py::arg("ncap"), py::arg("narena"), py::arg("ntomb"),
+          py::arg("counters"), py::arg("stream"));
 }

@@ -13,6 +13,7 @@
 #include "../dns/codec.hpp"
 #include "../engine/engine.hpp"
 #include "../engine/store.hpp"
+#include "../gpu/answerdelta.hpp"
 #include "../gpu/answerimage.hpp"
 #include "../server/fastparse.hpp"
 #include "../zk/hostlist.hpp"
@@ -427,6 +428,68 @@ PYBIND11_MODULE(_native, m) {
                                   t.arenaBytes());
              })
         .def("__len__", &gpu::AnswerImage::size);
+
+    /* a batch of changes to the device copy of such a table
+     * (gpu/answerdelta.hpp), kept in the normal form the update kernels
+     * apply; pack() hands out the packed sections as bytes */
+    py::class_<gpu::AnswerDelta>(m, "AnswerDelta")
+        .def(py::init<>())
+        .def("upsert_reply",
+             [](gpu::AnswerDelta& d, py::bytes qname, int qtype,
+                py::bytes reply) {
+                 try {
+                     d.upsertReply(std::string_view(qname), qtype,
+                                   std::string_view(reply));
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("qname"), py::arg("qtype"), py::arg("reply"))
+        .def("upsert_service",
+             [](gpu::AnswerDelta& d, py::bytes qname, int qtype,
+                py::bytes head,
+                const std::vector<std::pair<py::bytes, py::bytes>>& mem) {
+                 std::vector<gpu::Member> members;
+                 members.reserve(mem.size());
+                 for (const auto& [a, b] : mem)
+                     members.emplace_back(std::string_view(a),
+                                          std::string_view(b));
+                 try {
+                     d.upsertService(std::string_view(qname), qtype,
+                                     std::string_view(head), members);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("qname"), py::arg("qtype"), py::arg("head"),
+             py::arg("members"))
+        .def("invalidate",
+             [](gpu::AnswerDelta& d, py::bytes domain) {
+                 try {
+                     d.invalidate(std::string_view(domain));
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             },
+             py::arg("domain"))
+        .def("clear", &gpu::AnswerDelta::clear)
+        .def("pack",
+             [](const gpu::AnswerDelta& d) {
+                 gpu::AnswerDelta::Packed p = d.pack();
+                 auto raw = [](const auto& v) {
+                     return py::bytes((const char*)v.data(),
+                                      v.size() * sizeof(v[0]));
+                 };
+                 py::dict out;
+                 out["ibuf"] = py::bytes(p.ibuf);
+                 out["ioff"] = raw(p.ioff);
+                 out["ihash"] = raw(p.ihash);
+                 out["ubuf"] = py::bytes(p.ubuf);
+                 out["uoff"] = raw(p.uoff);
+                 out["uhash"] = raw(p.uhash);
+                 return out;
+             })
+        .def("__len__", &gpu::AnswerDelta::size);
 
     py::class_<PyStubEngine>(m, "StubEngine")
         .def(py::init<const std::string&, const std::string&, bool>(),

@@ -7,7 +7,9 @@ tree's shape: 10 000 hosts plus 100 services of 8 members (each service
 has its A and its SRV entry). Device events around resolve() and around
 each kernel on buffers allocated beforehand; warm-up first; median and
 min..max of the repeats. Bytes per query are the bytes the algorithm
-has to move, computed from the shapes, not counters.
+has to move, computed from the shapes, not counters. Then the table's
+upkeep: apply() of 1, 1 000 and 10 000 mixed ops and one compact(),
+next to constructing a GpuAnswerTable from the whole image again.
 
 The measurement runs in one child process under a time limit. Without a
 GPU or the extension the file says "not measured".
@@ -145,6 +147,34 @@ def worker(n: int, repeats: int) -> dict:
     res["kernel_qps"] = n / kernel_s
     res["kernel_gbps"] = (look_rd + 8 * n + emit_rd + emit_wr) / kernel_s / 1e9
     res["resolve_qps"] = n / (res["resolve"]["median_ms"] / 1e3)
+
+    # keeping the device table current: apply() of a mixed delta (half
+    # replacements, a quarter invalidations, a quarter new hosts) against
+    # the only way there was before it, uploading the whole image again
+    res["reupload"] = series(lambda: gpuresolve.GpuAnswerTable(image))
+    live = gpuresolve.GpuAnswerTable(image, reserve_entries=4 * len(image),
+                                     reserve_bytes=64 << 20)
+    fresh = iter(range(HOSTS, 10 ** 9))
+
+    def delta(ops):
+        d = _native.AnswerDelta()
+        for _ in range(ops):
+            kind, i = rng.random(), rng.randrange(HOSTS)
+            name = b"h%d.bench.foo.com" % i
+            if kind < 0.25:
+                d.invalidate(name)
+                continue
+            if kind < 0.5:
+                i = next(fresh)
+                name = b"h%d.bench.foo.com" % i
+            d.upsert_reply(name, 1, header(name, 1, 1, 0) + rr(
+                b"\xc0\x0c", 1, struct.pack(">I", 0x0A000000 + i % 2 ** 24)))
+        return d
+    for ops in (1, 1000, 10000):
+        deltas = iter([delta(ops) for _ in range(3 + max(20, repeats))])
+        res[f"apply{ops}"] = series(lambda: live.apply(next(deltas)))
+    res["compact"] = series(live.compact)
+    res["live"] = live.stats()
     return res
 
 
@@ -177,6 +207,11 @@ def render(res) -> str:
             row("bamd_resolve_lookup", "lookup") +
             row("bamd_resolve_emit", "emit") +
             row("download rbuf", "download") +
+            row("new GpuAnswerTable(image), the whole upload", "reupload") +
+            row("apply() of 1 op", "apply1") +
+            row("apply() of 1 000 mixed ops", "apply1000") +
+            row("apply() of 10 000 mixed ops", "apply10000") +
+            row("compact()", "compact") +
             f"\n- kernels: {res['kernel_qps'] / 1e6:.1f} M queries/s, "
             f"{res['kernel_gbps']:.1f} GB/s of needed bytes over kernel "
             "time\n"
@@ -185,7 +220,19 @@ def render(res) -> str:
             f"- bytes per query from the shapes: lookup reads "
             f"{b['lookup_read']:.1f} and writes {b['lookup_write']:.0f}; "
             f"emit reads {b['emit_read']:.1f} and writes "
-            f"{b['emit_write']:.1f}\n" + CONTEXT)
+            f"{b['emit_write']:.1f}\n"
+            "- apply() and the upload are whole calls between two device "
+            "events, host packing and copies included; a mixed delta is "
+            "half replacements, a quarter invalidations, a quarter new "
+            "hosts; an apply() that compacts first shows in its row's max\n"
+            "- apply() over the whole upload, by the medians: " +
+            ", ".join(
+                f"{ops} ops " + "%.2f" % (res[f"apply{ops}"]["median_ms"] /
+                                          res["reupload"]["median_ms"])
+                for ops in (1, 1000, 10000)) +
+            " (above 1 the delta costs more than uploading this "
+            f"{res['entries']}-entry image again)\n"
+            f"- the updated table at the end: {res['live']}\n" + CONTEXT)
 
 
 def main():
