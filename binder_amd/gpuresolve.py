@@ -11,7 +11,11 @@ The work is two hand-written gfx950 kernels (native/gpu/resolve.cpp):
 `bamd_resolve_lookup` parses, hashes and probes one query per lane,
 `bamd_resolve_emit` copies or assembles the replies into one packed
 buffer. torch is the plumbing only: it owns the buffers, the stream and
-the prefix sum between the two kernels. The table follows the registry
+the prefix sum between the two kernels. With `accept` set, resolve()
+runs a second pair instead (native/gpu/resolveext.cpp),
+`bamd_resolve_lookup_ext` and `bamd_resolve_emit_ext`, which also serve
+queries that carry an EDNS0 OPT record (ACCEPT_EDNS) or uppercase in the
+name (ACCEPT_ANYCASE). The table follows the registry
 through apply(): four more kernels (native/gpu/update.cpp) tombstone
 what a delta invalidates, claim or replace slots for what it upserts,
 and compact the table when dead space has built up. A query the image does not
@@ -47,6 +51,8 @@ TILE = _gpuresolve.TILE        # queries per lookup workgroup
 GROUP = _gpuresolve.GROUP      # lanes per reply in emit
 MAX_QUERY = _gpuresolve.MAX_QUERY
 OP_BLOCK = _gpuresolve.OP_BLOCK  # ops per update workgroup
+ACCEPT_EDNS = _gpuresolve.ACCEPT_EDNS        # ARCOUNT 1 with an OPT record
+ACCEPT_ANYCASE = _gpuresolve.ACCEPT_ANYCASE  # 'A'-'Z' in the name
 
 
 def _pow2(n):
@@ -208,10 +214,18 @@ class GpuAnswerTable:
                 "arena_bytes": self._used, "dead_bytes": dead,
                 "compactions": self.compactions}
 
-    def resolve(self, qbuf, qoff, seed=0):
+    def resolve(self, qbuf, qoff, seed=0, accept=0):
         """qbuf: uint8 query bytes end to end; qoff: int32 [N + 1].
-        Returns (rbuf uint8, roff int64 [N + 1]) on the device."""
+        Returns (rbuf uint8, roff int64 [N + 1]) on the device.
+
+        accept is a set of ACCEPT_EDNS and ACCEPT_ANYCASE: what to serve
+        beyond the CPU fast parser's queries. A query with a well-formed
+        OPT record gets the server's OPT appended and ARCOUNT + 1, unless
+        that passes the size it advertises; a name with uppercase is
+        looked up folded and echoed as asked."""
         dev = self.device
+        if accept & ~(ACCEPT_EDNS | ACCEPT_ANYCASE):
+            raise ValueError(f"unknown accept bits: {accept:#x}")
         if qbuf.dtype != torch.uint8 or qoff.dtype != torch.int32:
             raise TypeError("qbuf must be uint8 and qoff int32")
         if qoff.dim() != 1 or qoff.numel() < 1 or qbuf.dim() != 1:
@@ -226,24 +240,36 @@ class GpuAnswerTable:
         qoff = qoff.to(dev).contiguous()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream().cuda_stream
+            batch = (qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n)
             body_off = torch.empty(n, dtype=torch.int32, device=dev)
             rlen = torch.empty(n, dtype=torch.int32, device=dev)
-            _gpuresolve.lookup(
-                qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n,
-                self._slots.data_ptr(), self.cap, self._arena.data_ptr(),
-                body_off.data_ptr(), rlen.data_ptr(), stream)
+            if accept:
+                meta = torch.empty(n, dtype=torch.int32, device=dev)
+                _gpuresolve.lookup_ext(
+                    *batch, self._slots.data_ptr(), self.cap,
+                    self._arena.data_ptr(), accept, body_off.data_ptr(),
+                    rlen.data_ptr(), meta.data_ptr(), stream)
+            else:
+                _gpuresolve.lookup(
+                    *batch, self._slots.data_ptr(), self.cap,
+                    self._arena.data_ptr(), body_off.data_ptr(),
+                    rlen.data_ptr(), stream)
             roff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             roff[1:] = torch.cumsum(rlen, 0, dtype=torch.int64)
             rbuf = torch.empty(int(roff[-1]), dtype=torch.uint8, device=dev)
-            if rbuf.numel() != 0:
+            if rbuf.numel() != 0 and accept:
+                _gpuresolve.emit_ext(
+                    *batch, self._arena.data_ptr(), body_off.data_ptr(),
+                    rlen.data_ptr(), meta.data_ptr(), roff.data_ptr(),
+                    rbuf.data_ptr(), seed & (2 ** 64 - 1), stream)
+            elif rbuf.numel() != 0:
                 _gpuresolve.emit(
-                    qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n,
-                    self._arena.data_ptr(), body_off.data_ptr(),
+                    *batch, self._arena.data_ptr(), body_off.data_ptr(),
                     rlen.data_ptr(), roff.data_ptr(), rbuf.data_ptr(),
                     seed & (2 ** 64 - 1), stream)
         return rbuf, roff
 
-    def resolve_list(self, queries, seed=0):
+    def resolve_list(self, queries, seed=0, accept=0):
         """One reply (bytes) or None per query."""
         offs = [0]
         for q in queries:
@@ -251,7 +277,7 @@ class GpuAnswerTable:
         qbuf = torch.frombuffer(bytearray(b"".join(queries) or b"\0"),
                                 dtype=torch.uint8)[:offs[-1]]
         qoff = torch.tensor(offs, dtype=torch.int32)
-        rbuf, roff = self.resolve(qbuf, qoff, seed)
+        rbuf, roff = self.resolve(qbuf, qoff, seed, accept)
         data, roff = rbuf.cpu().numpy().tobytes(), roff.tolist()
         return [data[a:b] if b > a else None
                 for a, b in zip(roff, roff[1:])]

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "resolve.hpp"
+#include "resolveext.hpp"
 #include "update.hpp"
 
 namespace py = pybind11;
@@ -95,6 +96,51 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
           py::arg("roff"), py::arg("rbuf"), py::arg("seed"),
           py::arg("stream"));
+
+    m.attr("ACCEPT_EDNS") = kAcceptEdns;
+    m.attr("ACCEPT_ANYCASE") = kAcceptAnycase;
+
+    m.def("lookup_ext",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uintptr_t bodyOff, uintptr_t rlen,
+             uintptr_t meta, uintptr_t stream) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchLookupExt(batch(qbuf, qoff, qbytes, n), img,
+                                    accept, ptr<uint32_t>(bodyOff),
+                                    ptr<int32_t>(rlen), ptr<uint32_t>(meta),
+                                    ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_lookup_ext");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("body_off"), py::arg("rlen"),
+          py::arg("meta"), py::arg("stream"));
+
+    m.def("emit_ext",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t arena, uintptr_t bodyOff, uintptr_t rlen,
+             uintptr_t meta, uintptr_t roff, uintptr_t rbuf, uint64_t seed,
+             uintptr_t stream) {
+              Image img{nullptr, 0, ptr<const uint8_t>(arena)};
+              check(launchEmitExt(batch(qbuf, qoff, qbytes, n), img,
+                                  ptr<const uint32_t>(bodyOff),
+                                  ptr<const int32_t>(rlen),
+                                  ptr<const uint32_t>(meta),
+                                  ptr<const int64_t>(roff),
+                                  ptr<uint8_t>(rbuf), seed,
+                                  ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_emit_ext");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
+          py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
+          py::arg("seed"), py::arg("stream"));
 
     m.attr("OP_BLOCK") = kOpBlock;
     m.attr("COUNTERS") = (int)kCounters;

@@ -9,7 +9,10 @@ each kernel on buffers allocated beforehand; warm-up first; median and
 min..max of the repeats. Bytes per query are the bytes the algorithm
 has to move, computed from the shapes, not counters. Then the table's
 upkeep: apply() of 1, 1 000 and 10 000 mixed ops and one compact(),
-next to constructing a GpuAnswerTable from the whole image again.
+next to constructing a GpuAnswerTable from the whole image again. The
+opt-in kernel pair (accept=3) is timed against the base pair on the same
+batch, the two alternating repeat by repeat, and on that batch's EDNS +
+mixed-case version.
 
 The measurement runs in one child process under a time limit. Without a
 GPU or the extension the file says "not measured".
@@ -38,6 +41,16 @@ def labels(name: bytes) -> bytes:
 def query(name: bytes, qtype: int) -> bytes:
     return (struct.pack(">HHHHHH", 0x4242, 0x0100, 1, 0, 0, 0) +
             labels(name) + struct.pack(">HH", qtype, 1))
+
+
+def query_ext(q: bytes) -> bytes:
+    """A query() as a 0x20 resolver with EDNS sends it: every other
+    letter of the name uppercase, ARCOUNT 1, an OPT record advertising
+    1232 bytes."""
+    name = bytes(c - 32 if i % 2 and 97 <= c <= 122 else c
+                 for i, c in enumerate(q[12:-4]))
+    return (q[:10] + b"\0\1" + name + q[-4:] +
+            struct.pack(">BHHIH", 0, 41, 1232, 0, 0))
 
 
 def header(name: bytes, qtype: int, an: int, ar: int) -> bytes:
@@ -90,6 +103,7 @@ def worker(n: int, repeats: int) -> dict:
     rng = random.Random(1)
     picks = [rng.choice(srv_q) if rng.random() < 0.1 else rng.choice(a_q)
              for _ in range(n)]
+    ext = {q: query_ext(q) for q, *_ in a_q + srv_q}
     offs = [0]
     for p in picks:
         offs.append(offs[-1] + len(p[0]))
@@ -140,6 +154,43 @@ def worker(n: int, repeats: int) -> dict:
     res["emit"] = series(lambda: _gpuresolve.emit(
         *batch, table._arena.data_ptr(), body_off.data_ptr(),
         rlen.data_ptr(), roff.data_ptr(), rbuf.data_ptr(), 7, stream))
+    # the opt-in pair: same batch, base and opt-in alternating; then the
+    # same names asked in mixed case with an OPT record
+    ebuf = torch.frombuffer(bytearray(b"".join(
+        ext[p[0]] for p in picks)), dtype=torch.uint8).cuda()
+    eoff = torch.tensor([0] + [len(ext[p[0]]) for p in picks]).cumsum(0).to(
+        torch.int32).cuda()
+    got, goff = table.resolve(ebuf, eoff, seed=7, accept=3)
+    assert int(goff[-1]) == emit_wr + 11 * n
+    assert torch.equal(table.resolve(qbuf, qoff, seed=7, accept=3)[0], rbuf)
+    meta = torch.empty(n, dtype=torch.int32, device="cuda")
+    ebatch = (ebuf.data_ptr(), eoff.data_ptr(), ebuf.numel(), n)
+
+    def pair(bt, off, out):
+        return (lambda: _gpuresolve.lookup_ext(
+            *bt, table._slots.data_ptr(), table.cap, table._arena.data_ptr(),
+            3, body_off.data_ptr(), rlen.data_ptr(), meta.data_ptr(),
+            stream), lambda: _gpuresolve.emit_ext(
+                *bt, table._arena.data_ptr(), body_off.data_ptr(),
+                rlen.data_ptr(), meta.data_ptr(), off.data_ptr(),
+                out.data_ptr(), 7, stream))
+    runs = {"resolve0": lambda: table.resolve(qbuf, qoff, seed=7),
+            "resolve3": lambda: table.resolve(qbuf, qoff, seed=7, accept=3),
+            "resolve3_ext": lambda: table.resolve(ebuf, eoff, seed=7,
+                                                  accept=3)}
+    # each emit right behind its own lookup: they share body_off and rlen
+    runs["lookup3"], runs["emit3"] = pair(batch, roff, rbuf)
+    runs["lookup3_ext"], runs["emit3_ext"] = pair(ebatch, goff, got)
+    ms = {k: [] for k in runs}
+    for r in range(3 + repeats):
+        for k, fn in runs.items():
+            t = timed(fn)[0]
+            if r >= 3:
+                ms[k].append(t)
+    for k, v in ms.items():
+        v.sort()
+        res[k] = {"median_ms": statistics.median(v), "min_ms": v[0],
+                  "max_ms": v[-1]}
     kernel_s = (res["lookup"]["median_ms"] + res["emit"]["median_ms"]) / 1e3
     res["bytes_per_query"] = {"lookup_read": look_rd / n, "lookup_write": 8.0,
                               "emit_read": emit_rd / n,
@@ -212,6 +263,19 @@ def render(res) -> str:
             row("apply() of 1 000 mixed ops", "apply1000") +
             row("apply() of 10 000 mixed ops", "apply10000") +
             row("compact()", "compact") +
+            "\nThe opt-in pair (`accept=3`) against the base pair, the "
+            "seven calls alternating repeat by repeat; `plain` is the batch "
+            "above, `EDNS + mixed case` the same names with every other "
+            "letter uppercase and an OPT record:\n\n"
+            "| step | median ms | min .. max ms |\n|---|---|---|\n" +
+            row("resolve() accept=0, plain", "resolve0") +
+            row("resolve() accept=3, plain", "resolve3") +
+            row("resolve() accept=3, EDNS + mixed case", "resolve3_ext") +
+            row("bamd_resolve_lookup_ext, plain", "lookup3") +
+            row("bamd_resolve_emit_ext, plain", "emit3") +
+            row("bamd_resolve_lookup_ext, EDNS + mixed case",
+                "lookup3_ext") +
+            row("bamd_resolve_emit_ext, EDNS + mixed case", "emit3_ext") +
             f"\n- kernels: {res['kernel_qps'] / 1e6:.1f} M queries/s, "
             f"{res['kernel_gbps']:.1f} GB/s of needed bytes over kernel "
             "time\n"
@@ -221,6 +285,15 @@ def render(res) -> str:
             f"{b['lookup_read']:.1f} and writes {b['lookup_write']:.0f}; "
             f"emit reads {b['emit_read']:.1f} and writes "
             f"{b['emit_write']:.1f}\n"
+            "- opt-in over base on the plain batch, by the medians: "
+            "resolve() %.2f, lookup %.2f, emit %.2f; resolve() on the EDNS "
+            "+ mixed-case batch over the base pair on the plain one: %.2f "
+            "(11 more bytes in and out per query)\n" % (
+                res["resolve3"]["median_ms"] / res["resolve0"]["median_ms"],
+                res["lookup3"]["median_ms"] / res["lookup"]["median_ms"],
+                res["emit3"]["median_ms"] / res["emit"]["median_ms"],
+                res["resolve3_ext"]["median_ms"] /
+                res["resolve0"]["median_ms"]) +
             "- apply() and the upload are whole calls between two device "
             "events, host packing and copies included; a mixed delta is "
             "half replacements, a quarter invalidations, a quarter new "
