@@ -22,6 +22,17 @@ and compact the table when dead space has built up. A query the image does not
 answer gets an empty reply (`roff[i + 1] == roff[i]`); the caller sends
 it down the CPU path.
 
+resolve() reads the replies' total back to size `rbuf`, which suits a
+replay of a million queries. A serving loop's bursts go through a
+workspace instead:
+
+    burst = table.burst(64)              # buffers allocated once
+    rbuf, rstart, rlen = burst.resolve(qbuf, qoff)
+
+That is one launch of `bamd_resolve_fused` (native/gpu/resolvefused.cpp),
+which looks up, places and writes a tile of queries in one workgroup,
+with no allocation and no read back to the host.
+
 Nothing else in binder_amd imports this module: it needs the HIP
 extension and a GPU, and says which one is missing.
 """
@@ -50,6 +61,7 @@ _native = require_native()
 TILE = _gpuresolve.TILE        # queries per lookup workgroup
 GROUP = _gpuresolve.GROUP      # lanes per reply in emit
 MAX_QUERY = _gpuresolve.MAX_QUERY
+FUSED_TILE = _gpuresolve.FUSED_TILE  # queries per fused workgroup
 OP_BLOCK = _gpuresolve.OP_BLOCK  # ops per update workgroup
 ACCEPT_EDNS = _gpuresolve.ACCEPT_EDNS        # ARCOUNT 1 with an OPT record
 ACCEPT_ANYCASE = _gpuresolve.ACCEPT_ANYCASE  # 'A'-'Z' in the name
@@ -269,6 +281,14 @@ class GpuAnswerTable:
                     seed & (2 ** 64 - 1), stream)
         return rbuf, roff
 
+    def burst(self, max_queries, max_bytes=None, rbuf=None):
+        """A reusable ResolveBurst workspace for batches of at most
+        max_queries queries; see there. For a serving loop's bursts of
+        tens to thousands of queries. On a million-query replay the
+        fused kernel is several times slower than resolve()
+        (profiles/GPURESOLVE.md): replay keeps resolve()."""
+        return ResolveBurst(self, max_queries, max_bytes, rbuf)
+
     def resolve_list(self, queries, seed=0, accept=0):
         """One reply (bytes) or None per query."""
         offs = [0]
@@ -281,3 +301,97 @@ class GpuAnswerTable:
         data, roff = rbuf.cpu().numpy().tobytes(), roff.tolist()
         return [data[a:b] if b > a else None
                 for a, b in zip(roff, roff[1:])]
+
+
+class ResolveBurst:
+    """Buffers for GpuAnswerTable's single-launch resolve, allocated
+    once: `rbuf` of max_bytes (by default max_queries x (512 + 11), the
+    largest reply with the OPT tail, which cannot overflow), or the
+    caller's own uint8 device tensor, whose length is then the capacity;
+    `rstart` int64 and `rlen` int32 per query; two two-word cursors.
+
+    resolve() on device inputs is one kernel launch and one reset of a
+    cursor (a small fill behind the launch, for the next call) on the
+    current stream: no allocation, no read back, so bursts queue behind
+    each other. It reads the table's buffers at call time:
+    a workspace made before an apply() that rebuilt the table serves the
+    new one. The stream rule is the table's: current stream, and not
+    concurrent with apply() on another stream. One workspace serves one
+    call at a time and stays on one stream: the fill that readies the
+    next call's cursor is queued behind this call's launch.
+
+    Replies of one tile of FUSED_TILE consecutive queries are packed in
+    query order; tiles lie in `rbuf` in the order the device placed them.
+    A batch of at most FUSED_TILE queries therefore has resolve()'s
+    bytes and offsets. A tile that finds no room in `rbuf` is left
+    unserved as a whole and counted in dropped()."""
+
+    REPLY_MAX = 512 + 11
+
+    def __init__(self, table, max_queries, max_bytes=None, rbuf=None):
+        if max_queries < 1 or max_queries >= 2 ** 31:
+            raise ValueError("max_queries must be in [1, 2^31)")
+        dev = table.device
+        if rbuf is None:
+            if max_bytes is None:
+                max_bytes = max_queries * self.REPLY_MAX
+            rbuf = torch.empty(max_bytes, dtype=torch.uint8, device=dev)
+        elif max_bytes is not None:
+            raise ValueError("give max_bytes or rbuf, not both")
+        elif rbuf.dtype != torch.uint8 or rbuf.dim() != 1 or \
+                not rbuf.is_contiguous() or rbuf.device.type != dev.type:
+            raise TypeError("rbuf must be a contiguous 1-d uint8 tensor "
+                            "on the table's device")
+        self.table, self.max_queries = table, max_queries
+        self.rbuf = rbuf
+        self.rstart = torch.zeros(max_queries, dtype=torch.int64, device=dev)
+        self.rlen = torch.zeros(max_queries, dtype=torch.int32, device=dev)
+        # two cursors { bytes claimed, hits dropped }, used in turn: a
+        # call launches on one and then clears the other for the next
+        # call, so no fill stands between the caller and its kernel
+        self._cursor = torch.zeros(2, 2, dtype=torch.int64, device=dev)
+        self._cur = (self._cursor[0], self._cursor[1])
+        self._turn = 0
+        self._out = tuple(
+            (rbuf.data_ptr(), rbuf.numel(), c.data_ptr(),
+             self.rstart.data_ptr(), self.rlen.data_ptr())
+            for c in self._cur)
+
+    def resolve(self, qbuf, qoff, seed=0, accept=0):
+        """qbuf, qoff, seed and accept as in GpuAnswerTable.resolve().
+        Returns (rbuf, rstart [N], rlen [N]): views of the workspace,
+        valid until the next call on it. Reply i is
+        rbuf[rstart[i]:rstart[i] + rlen[i]]; rlen[i] == 0 means query i
+        is not served, and rstart[i] then means nothing."""
+        t = self.table
+        if accept & ~(ACCEPT_EDNS | ACCEPT_ANYCASE):
+            raise ValueError(f"unknown accept bits: {accept:#x}")
+        if qbuf.dtype != torch.uint8 or qoff.dtype != torch.int32:
+            raise TypeError("qbuf must be uint8 and qoff int32")
+        if qoff.dim() != 1 or qoff.numel() < 1 or qbuf.dim() != 1:
+            raise ValueError("qbuf and qoff must be 1-d, qoff [N + 1]")
+        if qbuf.numel() >= 2 ** 31:
+            raise ValueError("qbuf must be under 2^31 bytes")
+        n = qoff.numel() - 1
+        if n > self.max_queries:
+            raise ValueError(f"{n} queries in a workspace for "
+                             f"{self.max_queries}")
+        if n == 0:
+            return self.rbuf, self.rstart[:0], self.rlen[:0]
+        qbuf = qbuf.to(t.device).contiguous()
+        qoff = qoff.to(t.device).contiguous()
+        k = self._turn
+        self._turn = k ^ 1
+        with torch.cuda.device(t.device):
+            _gpuresolve.fused(
+                qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n,
+                t._slots.data_ptr(), t.cap, t._arena.data_ptr(), accept,
+                seed & (2 ** 64 - 1), *self._out[k],
+                torch.cuda.current_stream().cuda_stream)
+            self._cur[k ^ 1].zero_()
+        return self.rbuf, self.rstart[:n], self.rlen[:n]
+
+    def dropped(self):
+        """Hits of the last non-empty resolve() that found no room in
+        `rbuf`. The one call here that synchronises."""
+        return int(self._cur[self._turn ^ 1][1])

@@ -11,6 +11,7 @@
 
 #include "resolve.hpp"
 #include "resolveext.hpp"
+#include "resolvefused.hpp"
 #include "update.hpp"
 
 namespace py = pybind11;
@@ -141,6 +142,35 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
           py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
           py::arg("seed"), py::arg("stream"));
+
+    m.attr("FUSED_TILE") = kFusedTile;
+
+    m.def("fused",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uint64_t seed, uintptr_t rbuf,
+             uint64_t capacity, uintptr_t cursor, uintptr_t rstart,
+             uintptr_t rlen, uintptr_t stream) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              if (capacity >= (1ull << 63))
+                  throw std::invalid_argument("capacity above 2^63");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchFused(batch(qbuf, qoff, qbytes, n), img, accept,
+                                seed, ptr<uint8_t>(rbuf), capacity,
+                                ptr<uint64_t>(cursor), ptr<int64_t>(rstart),
+                                ptr<int32_t>(rlen),
+                                ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_fused");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("seed"), py::arg("rbuf"),
+          py::arg("capacity"), py::arg("cursor"), py::arg("rstart"),
+          py::arg("rlen"), py::arg("stream"));
 
     m.attr("OP_BLOCK") = kOpBlock;
     m.attr("COUNTERS") = (int)kCounters;

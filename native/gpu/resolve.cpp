@@ -28,92 +28,6 @@
 
 namespace bamd::gpu {
 
-namespace {
-
-/* One query: parseFastQuery()'s accept/reject decisions, then the
- * table walk of AnswerTable::find(). Leaves *bodyOff / *total alone
- * when the query is not served. */
-__device__ __forceinline__ void resolveOne(
-    const uint8_t* q, uint32_t len, const uint4* slots, uint32_t cap,
-    const uint8_t* arena, uint32_t* bodyOff, int32_t* total) {
-    if (len < 17 || len > (uint32_t)kMaxQuery) return;
-    /* flags: QR/opcode/AA/TC clear, RD free; byte 3 must be zero */
-    if (((q[2] & 0xFE) | q[3]) != 0) return;
-    /* counts: qd=1, an=ns=ar=0 */
-    if ((q[4] | (q[5] ^ 1) | q[6] | q[7] | q[8] | q[9] | q[10] |
-         q[11]) != 0)
-        return;
-
-    /* pass 1: walk the labels. nlen is the dotted name's length, p3
-     * the position of the third label's length byte, srvOk whether the
-     * first two labels are '_' followed by no further '_'. */
-    uint32_t pos = 12, nlen = 0, nlab = 0, p3 = 0;
-    bool srvOk = true;
-    while (true) {
-        if (pos >= len) return;
-        uint32_t l = q[pos++];
-        if (l == 0) break;
-        if ((l & 0xC0) != 0 || pos + l > len) return;
-        if (nlen + l + 1 > 256) return;
-        if (nlen > 0) ++nlen;
-        if (nlab == 2) p3 = pos - 1;
-        for (uint32_t k = 0; k < l; ++k) {
-            uint32_t c = q[pos + k];
-            bool ok = (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') ||
-                      c == '_' || c == '-';
-            if (!ok) return;
-            if (nlab < 2) srvOk &= (c == '_') == (k == 0);
-        }
-        nlen += l;
-        pos += l;
-        ++nlab;
-    }
-    if (pos + 4 > len) return;
-    uint32_t qtype = q[pos + 1];
-    if (q[pos] != 0 || (qtype != 1 && qtype != 33)) return;
-    if (q[pos + 2] != 0 || q[pos + 3] != 1) return;  /* class IN */
-
-    /* pass 2: hash. A: the whole name. SRV: from the third label on. */
-    KeyReader whole{q, 13, 13u + q[12]};
-    KeyReader hashed = whole;
-    uint32_t klen = nlen;
-    if (qtype == 33) {
-        if (nlab < 3 || !srvOk) return;
-        hashed = KeyReader{q, p3 + 1, p3 + 1 + q[p3]};
-        klen = nlen - (p3 - 12);
-    }
-    uint64_t h = hashKey(hashed, klen, qtype);
-    uint32_t hlo = (uint32_t)h, hhi = (uint32_t)(h >> 32);
-
-    /* probe: at most cap steps whatever the slots hold */
-    uint32_t mask = cap - 1;
-    uint32_t idx = hlo & mask;
-    for (uint32_t step = 0; step < cap; ++step, idx = (idx + 1) & mask) {
-        uint4 s = slots[idx];  /* hash lo, hash hi, off, len */
-        if (s.w == 0) return;
-        if (s.x != hlo || s.y != hhi) continue;
-        /* same hash: confirm klen, qtype and the whole name. nlen may
-         * be 256, which no blob's one-byte klen equals. */
-        const uint8_t* b = arena + s.z;
-        if (b[0] != nlen || b[1] != qtype) continue;
-        KeyReader r = whole;
-        bool same = true;
-        for (uint32_t k = 0; k < nlen; ++k) {
-            if (b[2 + k] != r.next()) {
-                same = false;
-                break;
-            }
-        }
-        if (!same) continue;
-        const uint8_t* body = b + 2 + nlen;
-        *bodyOff = s.z + 2 + nlen;
-        *total = (int32_t)(body[2] | ((uint32_t)body[3] << 8));
-        return;
-    }
-}
-
-}  // namespace
-
 extern "C" __global__ __launch_bounds__(kTile) void bamd_resolve_lookup(
     const uint8_t* __restrict__ qbuf, const int32_t* __restrict__ qoff,
     int64_t qbytes, int32_t n, const uint4* __restrict__ slots,

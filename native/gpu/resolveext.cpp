@@ -35,181 +35,6 @@
 
 namespace bamd::gpu {
 
-namespace {
-
-/* One query: parseFastQuery()'s decisions on the folded name and the
- * question alone, the OPT record's on what follows, then the table
- * walk. Leaves the outputs alone when the query is not served. */
-__device__ __forceinline__ void resolveOneExt(
-    const uint8_t* q, uint32_t len, uint32_t accept, const uint4* slots,
-    uint32_t cap, const uint8_t* arena, uint32_t* bodyOff, int32_t* total,
-    uint32_t* meta) {
-    if (len < 17 || len > (uint32_t)kMaxQuery) return;
-    /* flags: QR/opcode/AA/TC clear, RD free; byte 3 must be zero */
-    if (((q[2] & 0xFE) | q[3]) != 0) return;
-    /* counts: qd=1, an=ns=0; ar=0, or 1 where an OPT is accepted */
-    if ((q[4] | (q[5] ^ 1) | q[6] | q[7] | q[8] | q[9] | q[10]) != 0)
-        return;
-    uint32_t ar = q[11];
-    if (ar > (accept & kAcceptEdns)) return;
-    bool anycase = (accept & kAcceptAnycase) != 0;
-
-    /* pass 1: walk the labels, as the base lookup does, on the folded
-     * bytes */
-    uint32_t pos = 12, nlen = 0, nlab = 0, p3 = 0;
-    bool srvOk = true, folded = false;
-    while (true) {
-        if (pos >= len) return;
-        uint32_t l = q[pos++];
-        if (l == 0) break;
-        if ((l & 0xC0) != 0 || pos + l > len) return;
-        if (nlen + l + 1 > 256) return;
-        if (nlen > 0) ++nlen;
-        if (nlab == 2) p3 = pos - 1;
-        for (uint32_t k = 0; k < l; ++k) {
-            uint32_t c = q[pos + k];
-            if (anycase && c - 'A' < 26u) {
-                c |= 0x20;
-                folded = true;
-            }
-            bool ok = (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') ||
-                      c == '_' || c == '-';
-            if (!ok) return;
-            if (nlab < 2) srvOk &= (c == '_') == (k == 0);
-        }
-        nlen += l;
-        pos += l;
-        ++nlab;
-    }
-    if (pos + 4 > len) return;
-    uint32_t qtype = q[pos + 1];
-    if (q[pos] != 0 || (qtype != 1 && qtype != 33)) return;
-    if (q[pos + 2] != 0 || q[pos + 3] != 1) return;  /* class IN */
-    uint32_t nameWire = pos - 12;  /* at most 258 */
-
-    /* the OPT record: root name, type 41, class = advertised size, TTL
-     * = extended rcode, version, flags; rdata inside the query. Flags
-     * and options are not looked at. */
-    uint32_t limit = 0;
-    if (ar != 0) {
-        uint32_t at = pos + 4;
-        if (at + kOptLen > len) return;
-        const uint8_t* o = q + at;
-        if ((o[0] | o[1] | (o[2] ^ 41) | o[5] | o[6]) != 0) return;
-        uint32_t rdlen = ((uint32_t)o[9] << 8) | o[10];
-        if (at + kOptLen + rdlen > len) return;
-        uint32_t adv = ((uint32_t)o[3] << 8) | o[4];
-        limit = adv < 512 ? 512 : (adv > 4096 ? 4096 : adv);
-    }
-
-    /* pass 2: hash. A: the whole name. SRV: from the third label on. */
-    FoldReader whole{q, 13, 13u + q[12]};
-    FoldReader hashed = whole;
-    uint32_t klen = nlen;
-    if (qtype == 33) {
-        if (nlab < 3 || !srvOk) return;
-        hashed = FoldReader{q, p3 + 1, p3 + 1 + q[p3]};
-        klen = nlen - (p3 - 12);
-    }
-    uint64_t h = hashKey(hashed, klen, qtype);
-    uint32_t hlo = (uint32_t)h, hhi = (uint32_t)(h >> 32);
-
-    /* probe: at most cap steps whatever the slots hold */
-    uint32_t mask = cap - 1;
-    uint32_t idx = hlo & mask;
-    for (uint32_t step = 0; step < cap; ++step, idx = (idx + 1) & mask) {
-        uint4 s = slots[idx];  /* hash lo, hash hi, off, len */
-        if (s.w == 0) return;
-        if (s.x != hlo || s.y != hhi) continue;
-        const uint8_t* b = arena + s.z;
-        if (b[0] != nlen || b[1] != qtype) continue;
-        FoldReader r = whole;
-        bool same = true;
-        for (uint32_t k = 0; k < nlen; ++k) {
-            if (b[2 + k] != r.next()) {
-                same = false;
-                break;
-            }
-        }
-        if (!same) continue;
-        const uint8_t* body = b + 2 + nlen;
-        uint32_t t = get16(body + 2);
-        uint32_t m = nameWire;
-        if (ar != 0) {
-            /* the CPU path owns truncation */
-            if (t + kOptLen > limit) return;
-            t += kOptLen;
-            m |= kMetaEdns;
-        }
-        if (folded) m |= kMetaFolded;
-        *bodyOff = s.z + 2 + nlen;
-        *total = (int32_t)t;
-        *meta = m;
-        return;
-    }
-}
-
-/* the server's OPT record behind 4 bytes that groupCopy may read in
- * front of a source */
-__constant__ __attribute__((aligned(16))) uint8_t kOptSrc[16] = {
-    0, 0, 0, 0, 0x00, 0x00, 0x29, 0x05, 0x78, 0, 0, 0, 0, 0, 0, 0};
-
-constexpr int kMaxExtJobs = kMaxJobs + 2;
-
-enum Source : uint16_t {
-    kSrcBody = 0,   /* src counts from the answer body's start */
-    kSrcQuery = 1,  /* ... from the query's */
-    kSrcOpt = 2,    /* ... from the OPT record's */
-};
-
-struct ExtJob {
-    uint16_t source, src, dst, len;
-};
-
-/* A group's first lane: lay out reply `index` behind its 12 header
- * bytes. `len0` is the reply's length without the OPT tail. Returns
- * the number of jobs. */
-__device__ uint32_t planReply(const uint8_t* body, uint32_t len0,
-                              uint32_t meta, uint64_t seed, uint64_t index,
-                              uint8_t* order, ExtJob* jobs) {
-    bool service = body[0] == 1;
-    uint32_t n = service ? body[1] : 0;
-    uint32_t headLen = service ? get16(body + 4) : len0;
-    uint32_t headOff = service ? 6 + 8 * n : 4;
-    /* the name as asked, clipped to the head */
-    uint32_t echo = 0;
-    if ((meta & kMetaFolded) != 0) {
-        uint32_t end = 12 + (meta & kMetaNameMask);
-        echo = (end < headLen ? end : headLen) - 12;
-    }
-    uint32_t nj = 0;
-    if (echo != 0) jobs[nj++] = ExtJob{kSrcQuery, 12, 12, (uint16_t)echo};
-    uint32_t w = 12 + echo;
-    if (w != headLen)
-        jobs[nj++] = ExtJob{kSrcBody, (uint16_t)(headOff + w), (uint16_t)w,
-                            (uint16_t)(headLen - w)};
-    w = headLen;
-    if (service) {
-        const uint8_t* tab = body + 6;
-        uint32_t segOff = headOff + headLen;
-        drawOrder(n, seed, index, order);
-        for (uint32_t pass = 0; pass < 2; ++pass) {
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint8_t* e = tab + 8 * order[i] + 4 * pass;
-                uint32_t len = get16(e + 2);
-                jobs[nj++] = ExtJob{kSrcBody, (uint16_t)(segOff + get16(e)),
-                                    (uint16_t)w, (uint16_t)len};
-                w += len;
-            }
-        }
-    }
-    if ((meta & kMetaEdns) != 0)
-        jobs[nj++] = ExtJob{kSrcOpt, 0, (uint16_t)w, (uint16_t)kOptLen};
-    return nj;
-}
-
-}  // namespace
-
 extern "C" __global__ __launch_bounds__(kTile) void bamd_resolve_lookup_ext(
     const uint8_t* __restrict__ qbuf, const int32_t* __restrict__ qoff,
     int64_t qbytes, int32_t n, const uint4* __restrict__ slots,

@@ -12,7 +12,13 @@ upkeep: apply() of 1, 1 000 and 10 000 mixed ops and one compact(),
 next to constructing a GpuAnswerTable from the whole image again. The
 opt-in kernel pair (accept=3) is timed against the base pair on the same
 batch, the two alternating repeat by repeat, and on that batch's EDNS +
-mixed-case version.
+mixed-case version. Last, the single-launch path for bursts
+(table.burst(N).resolve) against resolve() on the first N queries of the
+same batch, N = 64, 256, 4096 and all, alternating repeat by repeat:
+device time between two events around the call, host wall time from
+the call until the reply lengths can be read on the host (resolve()
+reads the total back itself; the burst call is followed by a
+synchronise), and both per call for 100 calls queued in a row.
 
 The measurement runs in one child process under a time limit. Without a
 GPU or the extension the file says "not measured".
@@ -26,12 +32,14 @@ import statistics
 import struct
 import subprocess
 import sys
+import time
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 OUT = REPO / "profiles" / "GPURESOLVE.md"
 HOSTS, SERVICES, MEMBERS = 10_000, 100, 8
+BURSTS = (64, 256, 4096)
 
 
 def labels(name: bytes) -> bytes:
@@ -199,6 +207,63 @@ def worker(n: int, repeats: int) -> dict:
     res["kernel_gbps"] = (look_rd + 8 * n + emit_rd + emit_wr) / kernel_s / 1e9
     res["resolve_qps"] = n / (res["resolve"]["median_ms"] / 1e3)
 
+    # bursts: resolve() and the fused launch on the first N queries
+    def spread(v):
+        v = sorted(v)
+        return {"median_ms": statistics.median(v), "min_ms": v[0],
+                "max_ms": v[-1]}
+
+    def both(fn, sync):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ev[0].record()
+        fn()
+        ev[1].record()
+        if sync:
+            torch.cuda.synchronize()
+        wall = (time.perf_counter() - t) * 1e3
+        ev[1].synchronize()
+        return ev[0].elapsed_time(ev[1]), wall
+
+    def queued(fn, calls=100):
+        """Per call, `calls` calls in a row with no wait between them:
+        device time between two events around the run, and host time."""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ev[0].record()
+        for _ in range(calls):
+            fn()
+        ev[1].record()
+        host = (time.perf_counter() - t) * 1e3 / calls
+        ev[1].synchronize()
+        return {"device_ms": ev[0].elapsed_time(ev[1]) / calls,
+                "host_ms": host}
+    res["burst"] = {}
+    for bn in sorted({b for b in BURSTS if b < n} | {n}):
+        bq, bo = qbuf[:offs[bn]], qoff[:bn + 1]
+        ws = table.burst(bn)
+        want, woff = table.resolve(bq, bo, seed=7)
+        got, gstart, glen = ws.resolve(bq, bo, seed=7)
+        assert torch.equal(glen, (woff[1:] - woff[:-1]).int())
+        assert ws.dropped() == 0
+        if bn <= gpuresolve.FUSED_TILE:  # one tile: resolve()'s bytes
+            assert torch.equal(got[:want.numel()], want)
+            assert torch.equal(gstart, woff[:-1])
+        runs = {"resolve": (lambda: table.resolve(bq, bo, seed=7), False),
+                "burst": (lambda: ws.resolve(bq, bo, seed=7), True)}
+        ms = {k: ([], []) for k in runs}
+        for r in range(3 + repeats):
+            for k, (fn, sync) in runs.items():
+                dev, wall = both(fn, sync)
+                if r >= 3:
+                    ms[k][0].append(dev)
+                    ms[k][1].append(wall)
+        res["burst"][str(bn)] = {k: {"device": spread(d), "wall": spread(w),
+                                     "queued": queued(runs[k][0])}
+                                 for k, (d, w) in ms.items()}
+
     # keeping the device table current: apply() of a mixed delta (half
     # replacements, a quarter invalidations, a quarter new hosts) against
     # the only way there was before it, uploading the whole image again
@@ -246,6 +311,32 @@ def render(res) -> str:
         return (f"| {name} | {s['median_ms']:.3f} | {s['min_ms']:.3f} .. "
                 f"{s['max_ms']:.3f} |\n")
     b = res["bytes_per_query"]
+
+    def burst_rows():
+        out = ""
+        for bn, r in res["burst"].items():
+            for k, call in (("resolve", "resolve()"),
+                            ("burst", "burst.resolve()")):
+                d, w = r[k]["device"], r[k]["wall"]
+                out += (f"| {bn} | {call} | {d['median_ms']:.4f} | "
+                        f"{d['min_ms']:.4f} .. {d['max_ms']:.4f} | "
+                        f"{w['median_ms']:.4f} | {w['min_ms']:.4f} .. "
+                        f"{w['max_ms']:.4f} | "
+                        f"{r[k]['queued']['device_ms']:.4f} | "
+                        f"{r[k]['queued']['host_ms']:.4f} |\n")
+        return out
+    ratios = ", ".join(
+        "N = %s device %.2f, wall %.2f, queued device %.2f, queued host "
+        "%.2f" % (
+            bn, r["burst"]["device"]["median_ms"] /
+            r["resolve"]["device"]["median_ms"],
+            r["burst"]["wall"]["median_ms"] /
+            r["resolve"]["wall"]["median_ms"],
+            r["burst"]["queued"]["device_ms"] /
+            r["resolve"]["queued"]["device_ms"],
+            r["burst"]["queued"]["host_ms"] /
+            r["resolve"]["queued"]["host_ms"])
+        for bn, r in res["burst"].items())
     return (head + f"`scripts/gpuresolve_bench.py` on {res['device']}: "
             f"{res['n']} queries (90 % A, 10 % SRV), {res['entries']} "
             f"entries in {res['slots']} slots, {res['repeats']} repeats "
@@ -305,7 +396,29 @@ def render(res) -> str:
                 for ops in (1, 1000, 10000)) +
             " (above 1 the delta costs more than uploading this "
             f"{res['entries']}-entry image again)\n"
-            f"- the updated table at the end: {res['live']}\n" + CONTEXT)
+            f"- the updated table at the end: {res['live']}\n"
+            "\nBursts: `table.burst(N).resolve()`, one launch of "
+            "`bamd_resolve_fused` into a buffer made beforehand and one "
+            "reset of a cursor behind it, against `resolve()` on the first N queries of the "
+            "batch above, inputs on the device, the two alternating repeat "
+            "by repeat. `device` is the time between two events around the "
+            "call; `wall` is host time from the call until the reply "
+            "lengths can be read on the host: `resolve()` reads the total "
+            "back itself, the burst call is followed by a synchronise. "
+            "`queued` is 100 calls in a row with no wait between them, per "
+            "call: device time between two events around the run, and the "
+            "host's time. At 64 and 256 queries every column is launch and "
+            "host overhead more than kernel time.\n\n"
+            "| N | call | device median ms | min .. max | wall median ms | "
+            "min .. max | queued device ms | queued host ms |\n"
+            "|---|---|---|---|---|---|---|---|\n" + burst_rows() +
+            f"\n- burst over resolve() by the medians: {ratios}\n"
+            "- at 1 000 000 queries the fused kernel is the slower one: a "
+            "workgroup of 1024 lanes looks up in one wave and one workgroup "
+            "is resident per CU, which buys a burst's latency with a "
+            "replay's throughput. Replay keeps `resolve()`; a serving loop "
+            "uses `burst()`, whose call leaves the host after the launch "
+            "and queues behind the one before it\n" + CONTEXT)
 
 
 def main():
