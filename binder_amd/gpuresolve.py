@@ -15,8 +15,15 @@ the prefix sum between the two kernels. With `accept` set, resolve()
 runs a second pair instead (native/gpu/resolveext.cpp),
 `bamd_resolve_lookup_ext` and `bamd_resolve_emit_ext`, which also serve
 queries that carry an EDNS0 OPT record (ACCEPT_EDNS) or uppercase in the
-name (ACCEPT_ANYCASE). The table follows the registry
-through apply(): four more kernels (native/gpu/update.cpp) tombstone
+name (ACCEPT_ANYCASE). With `oversize=True` it runs a third pair
+(native/gpu/resolvelarge.cpp), `bamd_resolve_lookup_lim` and
+`bamd_resolve_emit_lim`, which serves an image built with a raised
+ceiling, `_native.AnswerImage(max_reply=4096)`: replies of up to 4096
+bytes, each held against what its query may take (512 bytes, or the OPT
+record's size clamped to [512, 4096]) and truncated as the server
+truncates when it does not fit: header with TC, the question, the OPT
+tail. The table follows the registry through apply(): four more
+kernels (native/gpu/update.cpp) tombstone
 what a delta invalidates, claim or replace slots for what it upserts,
 and compact the table when dead space has built up. A query the image does not
 answer gets an empty reply (`roff[i + 1] == roff[i]`); the caller sends
@@ -31,7 +38,9 @@ workspace instead:
 
 That is one launch of `bamd_resolve_fused` (native/gpu/resolvefused.cpp),
 which looks up, places and writes a tile of queries in one workgroup,
-with no allocation and no read back to the host.
+with no allocation and no read back to the host. The burst path has no
+`oversize` switch yet: on an image with a raised ceiling it leaves
+entries above 512 bytes unserved, as resolve() does without the switch.
 
 Nothing else in binder_amd imports this module: it needs the HIP
 extension and a GPU, and says which one is missing.
@@ -88,6 +97,7 @@ class GpuAnswerTable:
             raise TypeError("GpuAnswerTable takes an _native.AnswerImage")
         self.device = torch.device(device)
         slots, arena = image.slots(), image.arena()  # verified copies
+        self.max_reply = image.max_reply  # the image's ceiling on a reply
         self.cap = len(slots) // 16
         self.entries = len(image)  # exact as of the last compaction
         self._slots = self._upload(slots)
@@ -176,6 +186,10 @@ class GpuAnswerTable:
         safe concurrently with resolve() on another stream."""
         if not isinstance(delta, _native.AnswerDelta):
             raise TypeError("apply takes an _native.AnswerDelta")
+        if delta.max_reply > self.max_reply:
+            raise ValueError(
+                f"delta built for replies up to {delta.max_reply} bytes, "
+                f"table for {self.max_reply}")
         p = delta.pack()
         ni, nu = len(p["ioff"]) // 4 - 1, len(p["uoff"]) // 4 - 1
         ibytes, ubytes = len(p["ibuf"]), len(p["ubuf"])
@@ -226,7 +240,7 @@ class GpuAnswerTable:
                 "arena_bytes": self._used, "dead_bytes": dead,
                 "compactions": self.compactions}
 
-    def resolve(self, qbuf, qoff, seed=0, accept=0):
+    def resolve(self, qbuf, qoff, seed=0, accept=0, oversize=False):
         """qbuf: uint8 query bytes end to end; qoff: int32 [N + 1].
         Returns (rbuf uint8, roff int64 [N + 1]) on the device.
 
@@ -234,7 +248,14 @@ class GpuAnswerTable:
         beyond the CPU fast parser's queries. A query with a well-formed
         OPT record gets the server's OPT appended and ARCOUNT + 1, unless
         that passes the size it advertises; a name with uppercase is
-        looked up folded and echoed as asked."""
+        looked up folded and echoed as asked.
+
+        Without oversize a hit above 512 bytes (the table then has a
+        raised ceiling, max_reply) and a hit that passes the advertised
+        size are left unserved. With oversize=True every accepted hit is
+        served: in full when reply and OPT tail fit 512 bytes, or the
+        advertised size clamped to [512, 4096], else truncated to the
+        header with TC set, the question as asked and the OPT tail."""
         dev = self.device
         if accept & ~(ACCEPT_EDNS | ACCEPT_ANYCASE):
             raise ValueError(f"unknown accept bits: {accept:#x}")
@@ -255,7 +276,13 @@ class GpuAnswerTable:
             batch = (qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n)
             body_off = torch.empty(n, dtype=torch.int32, device=dev)
             rlen = torch.empty(n, dtype=torch.int32, device=dev)
-            if accept:
+            if oversize:
+                meta = torch.empty(n, dtype=torch.int32, device=dev)
+                _gpuresolve.lookup_lim(
+                    *batch, self._slots.data_ptr(), self.cap,
+                    self._arena.data_ptr(), accept, body_off.data_ptr(),
+                    rlen.data_ptr(), meta.data_ptr(), stream)
+            elif accept:
                 meta = torch.empty(n, dtype=torch.int32, device=dev)
                 _gpuresolve.lookup_ext(
                     *batch, self._slots.data_ptr(), self.cap,
@@ -269,7 +296,12 @@ class GpuAnswerTable:
             roff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             roff[1:] = torch.cumsum(rlen, 0, dtype=torch.int64)
             rbuf = torch.empty(int(roff[-1]), dtype=torch.uint8, device=dev)
-            if rbuf.numel() != 0 and accept:
+            if rbuf.numel() != 0 and oversize:
+                _gpuresolve.emit_lim(
+                    *batch, self._arena.data_ptr(), body_off.data_ptr(),
+                    rlen.data_ptr(), meta.data_ptr(), roff.data_ptr(),
+                    rbuf.data_ptr(), seed & (2 ** 64 - 1), stream)
+            elif rbuf.numel() != 0 and accept:
                 _gpuresolve.emit_ext(
                     *batch, self._arena.data_ptr(), body_off.data_ptr(),
                     rlen.data_ptr(), meta.data_ptr(), roff.data_ptr(),
@@ -289,7 +321,7 @@ class GpuAnswerTable:
         (profiles/GPURESOLVE.md): replay keeps resolve()."""
         return ResolveBurst(self, max_queries, max_bytes, rbuf)
 
-    def resolve_list(self, queries, seed=0, accept=0):
+    def resolve_list(self, queries, seed=0, accept=0, oversize=False):
         """One reply (bytes) or None per query."""
         offs = [0]
         for q in queries:
@@ -297,7 +329,7 @@ class GpuAnswerTable:
         qbuf = torch.frombuffer(bytearray(b"".join(queries) or b"\0"),
                                 dtype=torch.uint8)[:offs[-1]]
         qoff = torch.tensor(offs, dtype=torch.int32)
-        rbuf, roff = self.resolve(qbuf, qoff, seed, accept)
+        rbuf, roff = self.resolve(qbuf, qoff, seed, accept, oversize)
         data, roff = rbuf.cpu().numpy().tobytes(), roff.tolist()
         return [data[a:b] if b > a else None
                 for a, b in zip(roff, roff[1:])]
@@ -358,7 +390,9 @@ class ResolveBurst:
             for c in self._cur)
 
     def resolve(self, qbuf, qoff, seed=0, accept=0):
-        """qbuf, qoff, seed and accept as in GpuAnswerTable.resolve().
+        """qbuf, qoff, seed and accept as in GpuAnswerTable.resolve();
+        there is no oversize here yet, so a hit above 512 bytes or past
+        the advertised size is not served (rlen[i] == 0).
         Returns (rbuf, rstart [N], rlen [N]): views of the workspace,
         valid until the next call on it. Reply i is
         rbuf[rstart[i]:rstart[i] + rlen[i]]; rlen[i] == 0 means query i

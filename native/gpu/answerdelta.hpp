@@ -52,6 +52,10 @@ class AnswerDelta {
         std::vector<uint64_t> uhash;  /* [U] */
     };
 
+    explicit AnswerDelta(size_t maxReply = kMaxReply)
+        : maxReply_(checkCeiling(maxReply)) {}
+
+    size_t maxReply() const { return maxReply_; }
     size_t size() const { return domains_.size() + upserts_.size(); }
     size_t invalidations() const { return domains_.size(); }
     size_t upserts() const { return upserts_.size(); }
@@ -65,7 +69,7 @@ class AnswerDelta {
     void upsertReply(std::string_view qname, int qtype,
                      std::string_view reply) {
         uint64_t h = hashOf(qname, qtype);
-        checkReply(reply);
+        checkReply(reply, maxReply_);
         std::string blob = blobHead(
             qname, qtype, answerbody::wireBodyLen(reply.size()));
         answerbody::wireFill(body(blob, qname), (const uint8_t*)reply.data(),
@@ -79,7 +83,7 @@ class AnswerDelta {
         uint64_t h = hashOf(qname, qtype);
         answerbody::Seg s1[answerbody::kMaxMembers];
         answerbody::Seg s2[answerbody::kMaxMembers];
-        size_t segBytes = checkService(head, members, s1, s2);
+        size_t segBytes = checkService(head, members, maxReply_, s1, s2);
         std::string blob = blobHead(
             qname, qtype,
             answerbody::serviceBodyLen(members.size(), head.size(),
@@ -167,7 +171,7 @@ class AnswerDelta {
 
     void put(std::string_view qname, int qtype, uint64_t h,
              std::string blob) {
-        verifyBlob((const uint8_t*)blob.data(), blob.size());
+        verifyBlob((const uint8_t*)blob.data(), blob.size(), maxReply_);
         auto [it, fresh] = upserts_.insert_or_assign(
             modelKey(qname, qtype), Upsert{h, std::move(blob)});
         if (fresh && qtype == 33) srvByHash_.emplace(h, qname);
@@ -176,6 +180,7 @@ class AnswerDelta {
     std::set<std::string> domains_;
     std::map<std::string, Upsert> upserts_;   /* qtype byte + qname */
     std::multimap<uint64_t, std::string> srvByHash_;  /* pending SRV */
+    size_t maxReply_;
 };
 
 }  // namespace bamd::gpu

@@ -162,7 +162,7 @@ void round(std::mt19937& rng, size_t ops) {
             p.ubuf.substr(p.uoff[i], p.uoff[i + 1] - p.uoff[i]);
         /* an exact-size heap copy: a read past the blob is a report */
         std::vector<uint8_t> exact(blob.begin(), blob.end());
-        verifyBlob(exact.data(), exact.size());
+        verifyBlob(exact.data(), exact.size(), kMaxReply);
         size_t klen = exact[0];
         std::string name = blob.substr(2, klen);
         CHECK(p.uhash[i] == hashOf(name, exact[1]));
@@ -206,6 +206,32 @@ void checkRefusals() {
     refused([&](AnswerDelta& d) { d.upsertService("a", 1, "short", {}); });
     refused([&](AnswerDelta& d) { d.invalidate(""); });
     refused([&](AnswerDelta& d) { d.invalidate(std::string(256, 'a')); });
+
+    /* a ceiling of the producer's own: the same rules one size up */
+    AnswerDelta large(4096);
+    large.upsertReply("a", 1, std::string(4096, 'x'));
+    std::string seg(60, 's');  /* 12 + 64 x 61 = 3916 bytes */
+    large.upsertService("s", 1, ok, std::vector<Member>(64, {seg, "t"}));
+    bool threw = false;
+    try {
+        large.upsertReply("b", 1, std::string(4097, 'x'));
+    } catch (const std::invalid_argument&) {
+        threw = true;
+    }
+    CHECK(threw && large.size() == 2 && large.maxReply() == 4096);
+    AnswerDelta::Packed p = large.pack();
+    for (size_t i = 0; i < 2; ++i)
+        verifyBlob((const uint8_t*)p.ubuf.data() + p.uoff[i],
+                   (size_t)(p.uoff[i + 1] - p.uoff[i]), 4096);
+    for (size_t bad : {511, 4097}) {
+        threw = false;
+        try {
+            AnswerDelta d(bad);
+        } catch (const std::invalid_argument&) {
+            threw = true;
+        }
+        CHECK(threw);
+    }
 }
 
 }  // namespace

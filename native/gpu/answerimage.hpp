@@ -12,7 +12,8 @@
  *     the name behind _svc._proto);
  *   - every body is a `wire` or `service` layout of answerbody::, its
  *     reply at least a DNS header (12 bytes, all in the head) and at
- *     most 512 bytes, at most 64 members, every segment inside the blob
+ *     most max_reply bytes (512 unless the producer asks for a ceiling of
+ *     up to 4096), at most 64 members, every segment inside the blob
  *     and the segment lengths adding up to `total`;
  *   - off + len of every slot lies inside the arena, and the slot array
  *     is a power of two loaded to at most 1/2 (so a probe always ends).
@@ -33,6 +34,10 @@ class AnswerImage {
 
     using Member = gpu::Member;
 
+    explicit AnswerImage(size_t maxReply = gpu::kMaxReply)
+        : maxReply_(checkCeiling(maxReply)) {}
+
+    size_t maxReply() const { return maxReply_; }
     size_t size() const { return tab_.size(); }
     const AnswerTable& table() const { return tab_; }
 
@@ -45,7 +50,7 @@ class AnswerImage {
     void addReply(std::string_view qname, int qtype,
                   std::string_view reply) {
         uint64_t h = hashOf(qname, qtype);
-        checkReply(reply);
+        checkReply(reply, maxReply_);
         uint8_t* body = tab_.insert(
             h, (uint8_t)qtype, qname.data(), qname.size(),
             answerbody::wireBodyLen(reply.size()));
@@ -62,7 +67,7 @@ class AnswerImage {
         size_t n = members.size();
         answerbody::Seg s1[answerbody::kMaxMembers];
         answerbody::Seg s2[answerbody::kMaxMembers];
-        size_t segBytes = checkService(head, members, s1, s2);
+        size_t segBytes = checkService(head, members, maxReply_, s1, s2);
         uint8_t* body = tab_.insert(
             h, (uint8_t)qtype, qname.data(), qname.size(),
             answerbody::serviceBodyLen(n, head.size(), segBytes));
@@ -88,7 +93,7 @@ class AnswerImage {
             ++live;
             if ((size_t)sl[i].off + sl[i].len > used)
                 imageFail("blob outside the arena");
-            verifyBlob(arena + sl[i].off, sl[i].len);
+            verifyBlob(arena + sl[i].off, sl[i].len, maxReply_);
         }
         if (live != tab_.size()) imageFail("slot count mismatch");
     }
@@ -101,6 +106,7 @@ class AnswerImage {
     };
 
     AnswerTable tab_;
+    size_t maxReply_;
 };
 
 }  // namespace bamd::gpu

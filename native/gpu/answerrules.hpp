@@ -18,7 +18,11 @@
 
 namespace bamd::gpu {
 
+/* the default ceiling on a stored reply, and the range a producer may
+ * choose one from: 4096 is the largest size the server ever grants a
+ * query, so a longer body could only be answered truncated */
 constexpr size_t kMaxReply = 512;
+constexpr size_t kMaxReplyCeiling = 4096;
 constexpr size_t kMinReply = 12;
 
 /* a service member's first and second segment */
@@ -48,11 +52,22 @@ inline uint64_t hashOf(std::string_view qname, int qtype) {
                                 qname.size() - d2 - 1, 33);
 }
 
-inline void checkReply(std::string_view reply) {
+/* a producer's ceiling: kMaxReply .. kMaxReplyCeiling */
+inline size_t checkCeiling(size_t maxReply) {
+    if (maxReply < kMaxReply || maxReply > kMaxReplyCeiling)
+        throw std::invalid_argument("max_reply must be in [512, 4096]");
+    return maxReply;
+}
+
+[[noreturn]] inline void tooLong(size_t maxReply) {
+    throw std::invalid_argument("reply longer than " +
+                                std::to_string(maxReply) + " bytes");
+}
+
+inline void checkReply(std::string_view reply, size_t maxReply) {
     if (reply.size() < kMinReply)
         throw std::invalid_argument("reply shorter than a header");
-    if (reply.size() > kMaxReply)
-        throw std::invalid_argument("reply longer than 512 bytes");
+    if (reply.size() > maxReply) tooLong(maxReply);
 }
 
 /* Check a service's head and members and lay the members out as the
@@ -60,7 +75,8 @@ inline void checkReply(std::string_view reply) {
  * Returns the segments' bytes. */
 inline size_t checkService(std::string_view head,
                            const std::vector<Member>& members,
-                           answerbody::Seg* s1, answerbody::Seg* s2) {
+                           size_t maxReply, answerbody::Seg* s1,
+                           answerbody::Seg* s2) {
     size_t n = members.size();
     if (n > answerbody::kMaxMembers)
         throw std::invalid_argument("more than 64 members");
@@ -72,23 +88,22 @@ inline size_t checkService(std::string_view head,
         s1[i] = {(const uint8_t*)a.data(), a.size()};
         s2[i] = {(const uint8_t*)b.data(), b.size()};
         segBytes += a.size() + b.size();
-        if (segBytes > kMaxReply) break;
+        if (segBytes > maxReply) break;
     }
-    if (head.size() + segBytes > kMaxReply)
-        throw std::invalid_argument("reply longer than 512 bytes");
+    if (head.size() + segBytes > maxReply) tooLong(maxReply);
     return segBytes;
 }
 
 /* One finished blob `klen qtype key body` against the contract;
  * throws std::runtime_error naming the first rule broken. */
-inline void verifyBlob(const uint8_t* b, size_t len) {
+inline void verifyBlob(const uint8_t* b, size_t len, size_t maxReply) {
     using answerbody::get16;
     if (len < 2 || len < 2 + (size_t)b[0] + 4) imageFail("short blob");
     if (b[1] != 1 && b[1] != 33) imageFail("qtype not A or SRV");
     const uint8_t* body = b + 2 + b[0];
     size_t blen = len - 2 - b[0];
     size_t total = answerbody::total(body);
-    if (total < kMinReply || total > kMaxReply) imageFail("bad total");
+    if (total < kMinReply || total > maxReply) imageFail("bad total");
     if (answerbody::kind(body) == answerbody::kWire) {
         if (blen != answerbody::wireBodyLen(total))
             imageFail("wire body length");

@@ -12,6 +12,7 @@
 #include "resolve.hpp"
 #include "resolveext.hpp"
 #include "resolvefused.hpp"
+#include "resolvelarge.hpp"
 #include "update.hpp"
 
 namespace py = pybind11;
@@ -142,6 +143,52 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
           py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
           py::arg("seed"), py::arg("stream"));
+
+    m.attr("LIST_ABOVE") = kListAbove;
+
+    m.def("lookup_lim",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uintptr_t bodyOff, uintptr_t rlen,
+             uintptr_t meta, uintptr_t stream) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchLookupLim(batch(qbuf, qoff, qbytes, n), img,
+                                    accept, ptr<uint32_t>(bodyOff),
+                                    ptr<int32_t>(rlen), ptr<uint32_t>(meta),
+                                    ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_lookup_lim");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("body_off"), py::arg("rlen"),
+          py::arg("meta"), py::arg("stream"));
+
+    /* list_above: kListAbove, or 2^32 - 1 for one group per reply */
+    m.def("emit_lim",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t arena, uintptr_t bodyOff, uintptr_t rlen,
+             uintptr_t meta, uintptr_t roff, uintptr_t rbuf, uint64_t seed,
+             uintptr_t stream, uint32_t listAbove) {
+              Image img{nullptr, 0, ptr<const uint8_t>(arena)};
+              check(launchEmitLim(batch(qbuf, qoff, qbytes, n), img,
+                                  ptr<const uint32_t>(bodyOff),
+                                  ptr<const int32_t>(rlen),
+                                  ptr<const uint32_t>(meta),
+                                  ptr<const int64_t>(roff),
+                                  ptr<uint8_t>(rbuf), seed, listAbove,
+                                  ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_emit_lim");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
+          py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
+          py::arg("seed"), py::arg("stream"),
+          py::arg("list_above") = kListAbove);
 
     m.attr("FUSED_TILE") = kFusedTile;
 

@@ -1,8 +1,9 @@
 /*
- * binder-amd: device helpers shared by the two resolve kernel pairs
- * (resolve.cpp, resolveext.cpp) and the fused kernel (resolvefused.cpp):
- * the streamed key and its hash, the member-order generator, the two
- * per-query lookups and the copy plans of a reply. Device code only.
+ * binder-amd: device helpers shared by the three resolve kernel pairs
+ * (resolve.cpp, resolveext.cpp, resolvelarge.cpp) and the fused kernel
+ * (resolvefused.cpp): the streamed key and its hash, the member-order
+ * generator, the per-query lookups and the copy plans of a reply.
+ * Device code only.
  */
 #pragma once
 
@@ -10,6 +11,7 @@
 
 #include <cstdint>
 
+#include "devcopy.hpp"
 #include "resolveext.hpp"
 
 namespace bamd::gpu {
@@ -217,16 +219,28 @@ __device__ __forceinline__ void resolveOne(
         }
         if (!same) continue;
         const uint8_t* body = b + 2 + nlen;
+        uint32_t t = get16(body + 2);
+        /* only an image with a raised ceiling holds such an entry */
+        if (t > (uint32_t)kSmallReply) return;
         *bodyOff = s.z + 2 + nlen;
-        *total = (int32_t)(body[2] | ((uint32_t)body[3] << 8));
+        *total = (int32_t)t;
         return;
     }
 }
 
 /* One query: parseFastQuery()'s decisions on the folded name and the
  * question alone, the OPT record's on what follows, then the table
- * walk. Leaves the outputs alone when the query is not served. */
-__device__ __forceinline__ void resolveOneExt(
+ * walk. Leaves the outputs alone when the query is not served.
+ *
+ * kLim picks what a hit is held against. Without it a reply above
+ * kSmallReply, or one that passes the advertised size with the OPT
+ * tail, is left unserved. With it (resolvelarge.cpp) the query is
+ * served either way: in full when the reply and the tail fit the size
+ * the query may take, 512 without an OPT record, else truncated to
+ * header, question and tail, which *total then counts, with
+ * kMetaTrunc set. */
+template <bool kLim>
+__device__ __forceinline__ void resolveOneExtT(
     const uint8_t* q, uint32_t len, uint32_t accept, const uint4* slots,
     uint32_t cap, const uint8_t* arena, uint32_t* bodyOff, int32_t* total,
     uint32_t* meta) {
@@ -321,18 +335,73 @@ __device__ __forceinline__ void resolveOneExt(
         const uint8_t* body = b + 2 + nlen;
         uint32_t t = get16(body + 2);
         uint32_t m = nameWire;
-        if (ar != 0) {
+        uint32_t e = ar != 0 ? (uint32_t)kOptLen : 0;
+        if constexpr (kLim) {
+            if (t + e > (ar != 0 ? limit : (uint32_t)kSmallReply)) {
+                t = 12 + nameWire + 4;
+                m |= kMetaTrunc;
+            }
+        } else {
             /* the CPU path owns truncation */
-            if (t + kOptLen > limit) return;
-            t += kOptLen;
-            m |= kMetaEdns;
+            if (t > (uint32_t)kSmallReply) return;
+            if (ar != 0 && t + e > limit) return;
         }
+        t += e;
+        if (ar != 0) m |= kMetaEdns;
         if (folded) m |= kMetaFolded;
         *bodyOff = s.z + 2 + nlen;
         *total = (int32_t)t;
         *meta = m;
         return;
     }
+}
+
+__device__ __forceinline__ void resolveOneExt(
+    const uint8_t* q, uint32_t len, uint32_t accept, const uint4* slots,
+    uint32_t cap, const uint8_t* arena, uint32_t* bodyOff, int32_t* total,
+    uint32_t* meta) {
+    resolveOneExtT<false>(q, len, accept, slots, cap, arena, bodyOff, total,
+                          meta);
+}
+
+/* The lookup kernel of the opt-in pairs, one query per lane: stage the
+ * tile's span of qbuf in `tile` (LDS, kTileBytes + 16) at its global
+ * address mod 16, check qoff per tile and per query, resolve. */
+template <bool kLim>
+__device__ __forceinline__ void lookupTileExt(
+    uint8_t* tile, const uint8_t* qbuf, const int32_t* qoff, int64_t qbytes,
+    int32_t n, const uint4* slots, uint32_t cap, const uint8_t* arena,
+    uint32_t accept, uint32_t* bodyOff, int32_t* rlen, uint32_t* meta) {
+    int32_t t0 = (int32_t)blockIdx.x * kTile;
+    int32_t t1 = t0 + kTile < n ? t0 + kTile : n;
+    int64_t b0 = qoff[t0], b1 = qoff[t1];
+    bool spanOk = b0 >= 0 && b1 >= b0 && b1 <= qbytes;
+    /* a span above kTileBytes holds a query above kMaxQuery: leave it
+     * in global memory, its lanes parse from there */
+    bool staged = spanOk && b1 - b0 <= kTileBytes;
+    uint32_t shift = 0;
+    if (staged) {
+        shift = (uint32_t)(uintptr_t)(qbuf + b0) & 15u;
+        loadSpan<kTile>(tile + shift, qbuf + b0, (uint32_t)(b1 - b0));
+    }
+    __syncthreads();
+
+    int32_t i = t0 + (int32_t)threadIdx.x;
+    if (i >= t1) return;
+    int64_t o0 = qoff[i], o1 = qoff[i + 1];
+    uint32_t off = kUnserved, m = 0;
+    int32_t total = 0;
+    if (cap != 0 && spanOk && o0 >= b0 && o1 >= o0 && o1 <= b1 &&
+        o1 - o0 <= kMaxQuery) {
+        uint32_t len = (uint32_t)(o1 - o0);
+        const uint8_t* q =
+            staged ? tile + shift + (uint32_t)(o0 - b0) : qbuf + o0;
+        resolveOneExtT<kLim>(q, len, accept, slots, cap, arena, &off, &total,
+                             &m);
+    }
+    bodyOff[i] = off;
+    rlen[i] = total;
+    meta[i] = m;
 }
 
 /* the server's OPT record behind 4 bytes that groupCopy may read in
@@ -393,6 +462,17 @@ __device__ inline uint32_t planReply(const uint8_t* body, uint32_t len0,
     if ((meta & kMetaEdns) != 0)
         jobs[nj++] = ExtJob{kSrcOpt, 0, (uint16_t)w, (uint16_t)kOptLen};
     return nj;
+}
+
+/* A group's first lane: lay out a truncated reply behind its 12 header
+ * bytes - the question as it was asked, and the OPT tail when the
+ * query carried one. Returns the number of jobs. */
+__device__ inline uint32_t planTruncated(uint32_t meta, ExtJob* jobs) {
+    uint32_t qlen = (meta & kMetaNameMask) + 4;
+    jobs[0] = ExtJob{kSrcQuery, 12, 12, (uint16_t)qlen};
+    if ((meta & kMetaEdns) == 0) return 1;
+    jobs[1] = ExtJob{kSrcOpt, 0, (uint16_t)(12 + qlen), (uint16_t)kOptLen};
+    return 2;
 }
 
 }  // namespace bamd::gpu

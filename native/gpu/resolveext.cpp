@@ -45,35 +45,8 @@ extern "C" __global__ __launch_bounds__(kTile) void bamd_resolve_lookup_ext(
     __shared__ uint4 tile4[(kTileBytes + 16) / 16];
     uint8_t* tile = (uint8_t*)tile4;
 
-    int32_t t0 = (int32_t)blockIdx.x * kTile;
-    int32_t t1 = t0 + kTile < n ? t0 + kTile : n;
-    int64_t b0 = qoff[t0], b1 = qoff[t1];
-    bool spanOk = b0 >= 0 && b1 >= b0 && b1 <= qbytes;
-    /* a span above kTileBytes holds a query above kMaxQuery: leave it
-     * in global memory, its lanes parse from there */
-    bool staged = spanOk && b1 - b0 <= kTileBytes;
-    uint32_t shift = 0;
-    if (staged) {
-        shift = (uint32_t)(uintptr_t)(qbuf + b0) & 15u;
-        loadSpan<kTile>(tile + shift, qbuf + b0, (uint32_t)(b1 - b0));
-    }
-    __syncthreads();
-
-    int32_t i = t0 + (int32_t)threadIdx.x;
-    if (i >= t1) return;
-    int64_t o0 = qoff[i], o1 = qoff[i + 1];
-    uint32_t off = kUnserved, m = 0;
-    int32_t total = 0;
-    if (cap != 0 && spanOk && o0 >= b0 && o1 >= o0 && o1 <= b1 &&
-        o1 - o0 <= kMaxQuery) {
-        uint32_t len = (uint32_t)(o1 - o0);
-        const uint8_t* q =
-            staged ? tile + shift + (uint32_t)(o0 - b0) : qbuf + o0;
-        resolveOneExt(q, len, accept, slots, cap, arena, &off, &total, &m);
-    }
-    bodyOff[i] = off;
-    rlen[i] = total;
-    meta[i] = m;
+    lookupTileExt<false>(tile, qbuf, qoff, qbytes, n, slots, cap, arena,
+                         accept, bodyOff, rlen, meta);
 }
 
 extern "C" __global__ __launch_bounds__(kEmitBlock)

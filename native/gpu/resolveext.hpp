@@ -49,6 +49,13 @@ constexpr int kOptLen = 11;
 constexpr uint32_t kMetaNameMask = 0x1FF;
 constexpr uint32_t kMetaEdns = 1u << 9;    /* the query carried an OPT */
 constexpr uint32_t kMetaFolded = 1u << 10; /* a name byte was folded */
+/* the reply is header, question and OPT tail (resolvelarge.hpp only) */
+constexpr uint32_t kMetaTrunc = 1u << 11;
+
+/* the longest reply this pair and the base pair serve: what a query
+ * without an OPT record may take over UDP. An image with a raised
+ * ceiling may hold longer ones, which these kernels leave unserved. */
+constexpr int kSmallReply = 512;
 
 /* as launchLookup; rlen counts the OPT tail, meta[i] is written for
  * every query */

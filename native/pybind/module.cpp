@@ -374,7 +374,15 @@ PYBIND11_MODULE(_native, m) {
      * (gpu/answerimage.hpp); slots() and arena() hand out a verified
      * snapshot */
     py::class_<gpu::AnswerImage>(m, "AnswerImage")
-        .def(py::init<>())
+        .def(py::init([](size_t maxReply) {
+                 try {
+                     return gpu::AnswerImage(maxReply);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             }),
+             py::arg("max_reply") = gpu::kMaxReply)
+        .def_property_readonly("max_reply", &gpu::AnswerImage::maxReply)
         .def("add_reply",
              [](gpu::AnswerImage& im, py::bytes qname, int qtype,
                 py::bytes reply) {
@@ -433,7 +441,15 @@ PYBIND11_MODULE(_native, m) {
      * (gpu/answerdelta.hpp), kept in the normal form the update kernels
      * apply; pack() hands out the packed sections as bytes */
     py::class_<gpu::AnswerDelta>(m, "AnswerDelta")
-        .def(py::init<>())
+        .def(py::init([](size_t maxReply) {
+                 try {
+                     return gpu::AnswerDelta(maxReply);
+                 } catch (const std::invalid_argument& e) {
+                     throw py::value_error(e.what());
+                 }
+             }),
+             py::arg("max_reply") = gpu::kMaxReply)
+        .def_property_readonly("max_reply", &gpu::AnswerDelta::maxReply)
         .def("upsert_reply",
              [](gpu::AnswerDelta& d, py::bytes qname, int qtype,
                 py::bytes reply) {

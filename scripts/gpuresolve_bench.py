@@ -439,7 +439,11 @@ def main():
     res = json.loads(p.stdout.splitlines()[-1]) if p.returncode == 0 else None
     if res is None:
         print(p.stderr[-2000:], file=sys.stderr)
-    args.out.write_text(render(res))
+    # the "## Oversize" section at the end of the file is
+    # gpuresolve_oversize_bench.py's: keep it
+    old = args.out.read_text() if args.out.exists() else ""
+    _, mark, kept = old.partition("\n## Oversize\n")
+    args.out.write_text(render(res) + mark + kept)
     print(render(res))
     return 0 if res is not None else 1
 
