@@ -101,10 +101,12 @@ $(PYMOD): $(CORE_OBJS) $(BUILD)/native/pybind/module.o
 # kernels, launcher and binding in one hipcc run; links amdhip64 only
 GPU_SRCS := native/gpu/resolve.cpp native/gpu/resolveext.cpp \
 	native/gpu/resolvelarge.cpp native/gpu/resolvefused.cpp \
-	native/gpu/update.cpp native/gpu/pymodule.cpp
+	native/gpu/resolvefusedlim.cpp native/gpu/update.cpp \
+	native/gpu/pymodule.cpp
 $(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp native/gpu/resolveext.hpp \
 		native/gpu/resolvelarge.hpp native/gpu/resolvefused.hpp \
-		native/gpu/update.hpp native/gpu/devcopy.hpp \
+		native/gpu/resolvefusedlim.hpp native/gpu/update.hpp \
+		native/gpu/devcopy.hpp \
 		native/gpu/resolvedev.hpp
 	$(HIPCC) -x hip --offload-arch=$(HIP_ARCH) $(HIPFLAGS) -Wno-error \
 	    $(PY_INCLUDES) -shared $(GPU_SRCS) -o $@

@@ -38,9 +38,14 @@ workspace instead:
 
 That is one launch of `bamd_resolve_fused` (native/gpu/resolvefused.cpp),
 which looks up, places and writes a tile of queries in one workgroup,
-with no allocation and no read back to the host. The burst path has no
-`oversize` switch yet: on an image with a raised ceiling it leaves
-entries above 512 bytes unserved, as resolve() does without the switch.
+with no allocation and no read back to the host. A workspace made with
+`table.burst(64, oversize=True)` launches `bamd_resolve_fused_lim`
+(native/gpu/resolvefusedlim.cpp) instead, which serves what
+resolve(..., oversize=True) serves: replies of up to 4096 bytes, in full
+or truncated. It deals the copies of a long reply (a 64-member service,
+a 4 KiB wire reply in chunks) out to the whole workgroup. Without the
+switch the burst path leaves entries above 512 bytes unserved, as
+resolve() does.
 
 Nothing else in binder_amd imports this module: it needs the HIP
 extension and a GPU, and says which one is missing.
@@ -313,13 +318,15 @@ class GpuAnswerTable:
                     seed & (2 ** 64 - 1), stream)
         return rbuf, roff
 
-    def burst(self, max_queries, max_bytes=None, rbuf=None):
+    def burst(self, max_queries, max_bytes=None, rbuf=None, oversize=False):
         """A reusable ResolveBurst workspace for batches of at most
         max_queries queries; see there. For a serving loop's bursts of
         tens to thousands of queries. On a million-query replay the
         fused kernel is several times slower than resolve()
-        (profiles/GPURESOLVE.md): replay keeps resolve()."""
-        return ResolveBurst(self, max_queries, max_bytes, rbuf)
+        (profiles/GPURESOLVE.md): replay keeps resolve(). oversize is
+        resolve()'s switch; it belongs to the workspace because it
+        sizes the default buffer."""
+        return ResolveBurst(self, max_queries, max_bytes, rbuf, oversize)
 
     def resolve_list(self, queries, seed=0, accept=0, oversize=False):
         """One reply (bytes) or None per query."""
@@ -338,8 +345,10 @@ class GpuAnswerTable:
 class ResolveBurst:
     """Buffers for GpuAnswerTable's single-launch resolve, allocated
     once: `rbuf` of max_bytes (by default max_queries x (512 + 11), the
-    largest reply with the OPT tail, which cannot overflow), or the
-    caller's own uint8 device tensor, whose length is then the capacity;
+    largest reply with the OPT tail, or with oversize=True max_queries x
+    4096, the upper end of what a query may take: neither can overflow),
+    or the caller's own uint8 device tensor, whose length is then the
+    capacity;
     `rstart` int64 and `rlen` int32 per query; two two-word cursors.
 
     resolve() on device inputs is one kernel launch and one reset of a
@@ -356,17 +365,26 @@ class ResolveBurst:
     query order; tiles lie in `rbuf` in the order the device placed them.
     A batch of at most FUSED_TILE queries therefore has resolve()'s
     bytes and offsets. A tile that finds no room in `rbuf` is left
-    unserved as a whole and counted in dropped()."""
+    unserved as a whole and counted in dropped().
+
+    With oversize=True every call launches `bamd_resolve_fused_lim` and
+    serves every accepted hit, in full or truncated, as
+    GpuAnswerTable.resolve(..., oversize=True) does; on an image with
+    the default ceiling that only adds the truncation of replies that
+    pass the advertised size."""
 
     REPLY_MAX = 512 + 11
+    REPLY_MAX_OVERSIZE = 4096
 
-    def __init__(self, table, max_queries, max_bytes=None, rbuf=None):
+    def __init__(self, table, max_queries, max_bytes=None, rbuf=None,
+                 oversize=False):
         if max_queries < 1 or max_queries >= 2 ** 31:
             raise ValueError("max_queries must be in [1, 2^31)")
         dev = table.device
         if rbuf is None:
             if max_bytes is None:
-                max_bytes = max_queries * self.REPLY_MAX
+                max_bytes = max_queries * (
+                    self.REPLY_MAX_OVERSIZE if oversize else self.REPLY_MAX)
             rbuf = torch.empty(max_bytes, dtype=torch.uint8, device=dev)
         elif max_bytes is not None:
             raise ValueError("give max_bytes or rbuf, not both")
@@ -375,6 +393,9 @@ class ResolveBurst:
             raise TypeError("rbuf must be a contiguous 1-d uint8 tensor "
                             "on the table's device")
         self.table, self.max_queries = table, max_queries
+        self.oversize = bool(oversize)
+        self._launch = (_gpuresolve.fused_lim if oversize
+                        else _gpuresolve.fused)
         self.rbuf = rbuf
         self.rstart = torch.zeros(max_queries, dtype=torch.int64, device=dev)
         self.rlen = torch.zeros(max_queries, dtype=torch.int32, device=dev)
@@ -390,9 +411,10 @@ class ResolveBurst:
             for c in self._cur)
 
     def resolve(self, qbuf, qoff, seed=0, accept=0):
-        """qbuf, qoff, seed and accept as in GpuAnswerTable.resolve();
-        there is no oversize here yet, so a hit above 512 bytes or past
-        the advertised size is not served (rlen[i] == 0).
+        """qbuf, qoff, seed and accept as in GpuAnswerTable.resolve().
+        A workspace made without oversize does not serve a hit above 512
+        bytes or past the advertised size (rlen[i] == 0); one made with
+        it serves them in full or truncated.
         Returns (rbuf, rstart [N], rlen [N]): views of the workspace,
         valid until the next call on it. Reply i is
         rbuf[rstart[i]:rstart[i] + rlen[i]]; rlen[i] == 0 means query i
@@ -417,7 +439,7 @@ class ResolveBurst:
         k = self._turn
         self._turn = k ^ 1
         with torch.cuda.device(t.device):
-            _gpuresolve.fused(
+            self._launch(
                 qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n,
                 t._slots.data_ptr(), t.cap, t._arena.data_ptr(), accept,
                 seed & (2 ** 64 - 1), *self._out[k],

@@ -12,6 +12,7 @@
 #include "resolve.hpp"
 #include "resolveext.hpp"
 #include "resolvefused.hpp"
+#include "resolvefusedlim.hpp"
 #include "resolvelarge.hpp"
 #include "update.hpp"
 
@@ -218,6 +219,45 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("accept"), py::arg("seed"), py::arg("rbuf"),
           py::arg("capacity"), py::arg("cursor"), py::arg("rstart"),
           py::arg("rlen"), py::arg("stream"));
+
+    m.attr("FUSED_LIST_ABOVE") = kFusedListAbove;
+    m.attr("FUSED_CHUNK") = kFusedChunk;
+    m.attr("FUSED_MIN_CHUNK") = kFusedMinChunk;
+
+    /* list_above, chunk: the defaults, or 2^32 - 1 for one group per
+     * reply */
+    m.def("fused_lim",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uint64_t seed, uintptr_t rbuf,
+             uint64_t capacity, uintptr_t cursor, uintptr_t rstart,
+             uintptr_t rlen, uintptr_t stream, uint32_t listAbove,
+             uint32_t chunk) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              if (capacity >= (1ull << 63))
+                  throw std::invalid_argument("capacity above 2^63");
+              if (chunk < kFusedMinChunk)
+                  throw std::invalid_argument("chunk below FUSED_MIN_CHUNK");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchFusedLim(batch(qbuf, qoff, qbytes, n), img, accept,
+                                   seed, ptr<uint8_t>(rbuf), capacity,
+                                   ptr<uint64_t>(cursor),
+                                   ptr<int64_t>(rstart), ptr<int32_t>(rlen),
+                                   listAbove, chunk,
+                                   ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_fused_lim");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("seed"), py::arg("rbuf"),
+          py::arg("capacity"), py::arg("cursor"), py::arg("rstart"),
+          py::arg("rlen"), py::arg("stream"),
+          py::arg("list_above") = kFusedListAbove,
+          py::arg("chunk") = kFusedChunk);
 
     m.attr("OP_BLOCK") = kOpBlock;
     m.attr("COUNTERS") = (int)kCounters;
