@@ -101,11 +101,12 @@ $(PYMOD): $(CORE_OBJS) $(BUILD)/native/pybind/module.o
 # kernels, launcher and binding in one hipcc run; links amdhip64 only
 GPU_SRCS := native/gpu/resolve.cpp native/gpu/resolveext.cpp \
 	native/gpu/resolvelarge.cpp native/gpu/resolvefused.cpp \
-	native/gpu/resolvefusedlim.cpp native/gpu/update.cpp \
-	native/gpu/pymodule.cpp
+	native/gpu/resolvefusedlim.cpp native/gpu/resolveframes.cpp \
+	native/gpu/update.cpp native/gpu/pymodule.cpp
 $(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp native/gpu/resolveext.hpp \
 		native/gpu/resolvelarge.hpp native/gpu/resolvefused.hpp \
-		native/gpu/resolvefusedlim.hpp native/gpu/update.hpp \
+		native/gpu/resolvefusedlim.hpp native/gpu/resolveframes.hpp \
+		native/gpu/update.hpp \
 		native/gpu/devcopy.hpp \
 		native/gpu/resolvedev.hpp
 	$(HIPCC) -x hip --offload-arch=$(HIP_ARCH) $(HIPFLAGS) -Wno-error \
@@ -119,7 +120,7 @@ test: all
 # Lint/style gate (parity with the reference's eslint/jsstyle/cstyle
 # gates, /root/reference/Makefile:17-20): C++ and Python style checks in
 # tools/lint.py; -Werror already covers compiler diagnostics.
-check: all
+check: all check-frameindex
 	$(PYTHON) -m py_compile binder_amd/*.py bench.py __graft_entry__.py
 	$(PYTHON) tools/lint.py
 	@echo "check OK"
@@ -166,6 +167,20 @@ $(BUILD)/answerdelta_check: native/gpu/answerdelta_check_main.cpp \
 
 check-answerdelta: $(BUILD)/answerdelta_check
 	$(BUILD)/answerdelta_check 1 300
+
+# Sanitizer run of the GPU resolver's frame indexer (gpu/frameindex.hpp)
+# in a stand-alone program: a run of frames of every type cut at every
+# byte, bad magic and oversized lengths mid-run, max_frames reached.
+# Host-only, CPU-only.
+$(BUILD)/frameindex_check: native/gpu/frameindex_check_main.cpp \
+		native/gpu/frameindex.hpp native/balancer/protocol.hpp
+	@mkdir -p $(BUILD)
+	$(CXX) -O1 -g -std=c++20 -Wall -Wextra -Werror \
+	    -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    $< -o $@
+
+check-frameindex: $(BUILD)/frameindex_check
+	$(BUILD)/frameindex_check
 
 # Sanitizer run of the balancer's reply-run grouping (replyruns.hpp) in a
 # stand-alone program with a recording sink: fixed and seeded random
@@ -323,6 +338,6 @@ clean:
 -include $(shell find $(BUILD) -name '*.d' 2>/dev/null)
 
 .PHONY: all clean test check check-framebuf check-answertab \
-	check-answerdelta \
+	check-answerdelta check-frameindex \
 	check-replyruns check-shmpipe check-bsocklink check-serve-threads \
 	check-codec check-wire-asan check-zkhosts release

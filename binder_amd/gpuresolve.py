@@ -47,6 +47,23 @@ a 4 KiB wire reply in chunks) out to the whole workgroup. Without the
 switch the burst path leaves entries above 512 bytes unserved, as
 resolve() does.
 
+What a serving loop holds is not bare DNS messages but a run of bsock1
+frames (native/balancer/protocol.hpp), and what it owes the balancer is
+REPLY frames. A third workspace takes and gives exactly that:
+
+    frames = table.frames(64)            # buffers allocated once
+    rbuf, rstart, rlen, miss = frames.resolve(fbuf, foff)
+
+`foff` is where the frames start, from `_native.frame_index` on the host
+(native/gpu/frameindex.hpp). One launch of `bamd_resolve_frames`
+(native/gpu/resolveframes.cpp) checks every frame against that index,
+reads the DNS message of a QUERY frame in place, serves it as the
+oversize burst does, and writes the REPLY frame header with the reply.
+A QUERY frame's `proto` byte says TCP or UDP, so TCP is served here: a
+hit comes back in full whatever its size. `rbuf[:frames.end()]` is a
+gap-free run of REPLY frames; `miss[:frames.misses()]` lists the frames
+left to the CPU path.
+
 Nothing else in binder_amd imports this module: it needs the HIP
 extension and a GPU, and says which one is missing.
 """
@@ -328,6 +345,12 @@ class GpuAnswerTable:
         sizes the default buffer."""
         return ResolveBurst(self, max_queries, max_bytes, rbuf, oversize)
 
+    def frames(self, max_frames, max_bytes=None, rbuf=None):
+        """A reusable FrameBurst workspace for runs of at most max_frames
+        bsock1 frames; see there. What a serving loop holds goes in as
+        it lies in the ring, and REPLY frames come out."""
+        return FrameBurst(self, max_frames, max_bytes, rbuf)
+
     def resolve_list(self, queries, seed=0, accept=0, oversize=False):
         """One reply (bytes) or None per query."""
         offs = [0]
@@ -451,3 +474,129 @@ class ResolveBurst:
         """Hits of the last non-empty resolve() that found no room in
         `rbuf`. The one call here that synchronises."""
         return int(self._cur[self._turn ^ 1][1])
+
+
+class FrameBurst:
+    """Buffers for GpuAnswerTable's single-launch resolve of a run of
+    bsock1 frames (native/balancer/protocol.hpp), allocated once: `rbuf`
+    of max_bytes (by default max_frames x REPLY_MAX, the longest REPLY
+    frame, which cannot overflow), or the caller's own uint8 device
+    tensor, whose length is then the capacity; `rstart` int64, `rlen`
+    and `miss` int32 per frame; two four-word cursors.
+
+    resolve() on device inputs is one launch of `bamd_resolve_frames`
+    and one reset of a cursor on the current stream: no allocation, no
+    read back. Streams, the table's buffers and "one call at a time"
+    are as for ResolveBurst.
+
+    A QUERY frame whose DNS message the table answers gets a REPLY
+    frame with its req_id. proto 0 is served as
+    burst(oversize=True) serves the bare message: in full when it fits
+    512 bytes or the advertised size, else truncated. Any other proto is
+    TCP, and a hit comes back in full whatever its size. `rbuf[:end()]`
+    is a gap-free run of whole REPLY frames, ready for the reply ring in
+    one copy: a tile's in frame order, tiles in the order the device
+    placed them. Every other frame (PING and the other types, a QUERY
+    that is malformed, not accepted or not in the table, a tile that
+    found no room in `rbuf`) is listed once in `miss[:misses()]`, for
+    the CPU path."""
+
+    REPLY_MAX = _gpuresolve.FRAMES_REPLY_MAX
+
+    def __init__(self, table, max_frames, max_bytes=None, rbuf=None):
+        if max_frames < 1 or max_frames >= 2 ** 31:
+            raise ValueError("max_frames must be in [1, 2^31)")
+        dev = table.device
+        if rbuf is None:
+            if max_bytes is None:
+                max_bytes = max_frames * self.REPLY_MAX
+            rbuf = torch.empty(max_bytes, dtype=torch.uint8, device=dev)
+        elif max_bytes is not None:
+            raise ValueError("give max_bytes or rbuf, not both")
+        elif rbuf.dtype != torch.uint8 or rbuf.dim() != 1 or \
+                not rbuf.is_contiguous() or rbuf.device.type != dev.type:
+            raise TypeError("rbuf must be a contiguous 1-d uint8 tensor "
+                            "on the table's device")
+        self.table, self.max_frames = table, max_frames
+        self.rbuf = rbuf
+        self.rstart = torch.zeros(max_frames, dtype=torch.int64, device=dev)
+        self.rlen = torch.zeros(max_frames, dtype=torch.int32, device=dev)
+        self.miss = torch.zeros(max_frames, dtype=torch.int32, device=dev)
+        # two cursors { bytes claimed, hits dropped, end of the stream,
+        # misses }, used in turn as ResolveBurst's are
+        self._cursor = torch.zeros(2, 4, dtype=torch.int64, device=dev)
+        self._cur = (self._cursor[0], self._cursor[1])
+        self._turn = 0
+        self._out = tuple(
+            (rbuf.data_ptr(), rbuf.numel(), c.data_ptr(),
+             self.rstart.data_ptr(), self.rlen.data_ptr(),
+             self.miss.data_ptr())
+            for c in self._cur)
+
+    def resolve(self, fbuf, foff, seed=0, accept=0):
+        """fbuf: uint8 frame bytes as they lie in the ring; foff: int32
+        [N + 1] frame starts, as _native.frame_index gives them; seed and
+        accept as in GpuAnswerTable.resolve().
+        Returns (rbuf, rstart [N], rlen [N], miss [N]): views of the
+        workspace, valid until the next call on it. Frame i's REPLY
+        frame is rbuf[rstart[i]:rstart[i] + rlen[i]]; rlen[i] == 0 means
+        it has none and i is in miss[:misses()]."""
+        t = self.table
+        if accept & ~(ACCEPT_EDNS | ACCEPT_ANYCASE):
+            raise ValueError(f"unknown accept bits: {accept:#x}")
+        if fbuf.dtype != torch.uint8 or foff.dtype != torch.int32:
+            raise TypeError("fbuf must be uint8 and foff int32")
+        if foff.dim() != 1 or foff.numel() < 1 or fbuf.dim() != 1:
+            raise ValueError("fbuf and foff must be 1-d, foff [N + 1]")
+        if fbuf.numel() >= 2 ** 31:
+            raise ValueError("fbuf must be under 2^31 bytes")
+        n = foff.numel() - 1
+        if n > self.max_frames:
+            raise ValueError(f"{n} frames in a workspace for "
+                             f"{self.max_frames}")
+        if n == 0:
+            return self.rbuf, self.rstart[:0], self.rlen[:0], self.miss[:0]
+        fbuf = fbuf.to(t.device).contiguous()
+        foff = foff.to(t.device).contiguous()
+        k = self._turn
+        self._turn = k ^ 1
+        with torch.cuda.device(t.device):
+            _gpuresolve.frames(
+                fbuf.data_ptr(), foff.data_ptr(), fbuf.numel(), n,
+                t._slots.data_ptr(), t.cap, t._arena.data_ptr(), accept,
+                seed & (2 ** 64 - 1), *self._out[k],
+                torch.cuda.current_stream().cuda_stream)
+            self._cur[k ^ 1].zero_()
+        return self.rbuf, self.rstart[:n], self.rlen[:n], self.miss[:n]
+
+    # of the last non-empty resolve(); these three synchronise
+
+    def end(self):
+        """Where the run of REPLY frames in `rbuf` ends."""
+        return int(self._cur[self._turn ^ 1][2])
+
+    def misses(self):
+        """How many frames are listed in `miss`."""
+        return int(self._cur[self._turn ^ 1][3])
+
+    def dropped(self):
+        """Hits that found no room in `rbuf`; they are in `miss` too."""
+        return int(self._cur[self._turn ^ 1][1])
+
+    def resolve_bytes(self, data, seed=0, accept=0):
+        """Index the whole frames at the front of `data`, at most
+        max_frames of them (_native.frame_index), upload, resolve and
+        read back: (the REPLY frames as bytes, the sorted indices of the
+        frames left to the CPU path, bytes of `data` consumed). For
+        replay and tests; a caller that must tell a cut frame from a bad
+        one behind `consumed` runs frame_index itself."""
+        foff, consumed, _ = _native.frame_index(data, self.max_frames)
+        n = len(foff) // 4 - 1
+        if n == 0:
+            return b"", [], consumed
+        rbuf, _, _, miss = self.resolve(
+            torch.frombuffer(bytearray(data[:consumed]), dtype=torch.uint8),
+            torch.frombuffer(bytearray(foff), dtype=torch.int32),
+            seed, accept)
+        return (rbuf[:self.end()].cpu().numpy().tobytes(),
+                sorted(miss[:self.misses()].tolist()), consumed)

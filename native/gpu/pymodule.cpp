@@ -11,6 +11,7 @@
 
 #include "resolve.hpp"
 #include "resolveext.hpp"
+#include "resolveframes.hpp"
 #include "resolvefused.hpp"
 #include "resolvefusedlim.hpp"
 #include "resolvelarge.hpp"
@@ -256,6 +257,43 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("accept"), py::arg("seed"), py::arg("rbuf"),
           py::arg("capacity"), py::arg("cursor"), py::arg("rstart"),
           py::arg("rlen"), py::arg("stream"),
+          py::arg("list_above") = kFusedListAbove,
+          py::arg("chunk") = kFusedChunk);
+
+    m.attr("FRAMES_REPLY_MAX") = kFramesReplyMax;
+
+    /* fbuf, foff: a run of bsock1 frames and its n + 1 frame starts;
+     * cursor: four 64-bit words, zero; miss: n int32 */
+    m.def("frames",
+          [](uintptr_t fbuf, uintptr_t foff, int64_t fbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uint64_t seed, uintptr_t rbuf,
+             uint64_t capacity, uintptr_t cursor, uintptr_t rstart,
+             uintptr_t rlen, uintptr_t miss, uintptr_t stream,
+             uint32_t listAbove, uint32_t chunk) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              if (capacity >= (1ull << 63))
+                  throw std::invalid_argument("capacity above 2^63");
+              if (chunk < kFusedMinChunk)
+                  throw std::invalid_argument("chunk below FUSED_MIN_CHUNK");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchFrames(batch(fbuf, foff, fbytes, n), img, accept,
+                                 seed, ptr<uint8_t>(rbuf), capacity,
+                                 ptr<uint64_t>(cursor), ptr<int64_t>(rstart),
+                                 ptr<int32_t>(rlen), ptr<int32_t>(miss),
+                                 listAbove, chunk,
+                                 ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_frames");
+          },
+          py::arg("fbuf"), py::arg("foff"), py::arg("fbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("seed"), py::arg("rbuf"),
+          py::arg("capacity"), py::arg("cursor"), py::arg("rstart"),
+          py::arg("rlen"), py::arg("miss"), py::arg("stream"),
           py::arg("list_above") = kFusedListAbove,
           py::arg("chunk") = kFusedChunk);
 

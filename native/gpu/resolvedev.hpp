@@ -1,8 +1,9 @@
 /*
  * binder-amd: device helpers shared by the three resolve kernel pairs
- * (resolve.cpp, resolveext.cpp, resolvelarge.cpp) and the fused kernel
- * (resolvefused.cpp): the streamed key and its hash, the member-order
- * generator, the per-query lookups and the copy plans of a reply.
+ * (resolve.cpp, resolveext.cpp, resolvelarge.cpp) and the fused kernels
+ * (resolvefused.cpp, resolvefusedlim.cpp, resolveframes.cpp): the
+ * streamed key and its hash, the member-order generator, the per-query
+ * lookups and the copy plans of a reply.
  * Device code only.
  */
 #pragma once
@@ -238,12 +239,13 @@ __device__ __forceinline__ void resolveOne(
  * served either way: in full when the reply and the tail fit the size
  * the query may take, 512 without an OPT record, else truncated to
  * header, question and tail, which *total then counts, with
- * kMetaTrunc set. */
+ * kMetaTrunc set. A non-zero `fixedLimit` is that size whatever the
+ * query says: 65535 for a query that came over TCP (resolveframes.cpp). */
 template <bool kLim>
 __device__ __forceinline__ void resolveOneExtT(
     const uint8_t* q, uint32_t len, uint32_t accept, const uint4* slots,
     uint32_t cap, const uint8_t* arena, uint32_t* bodyOff, int32_t* total,
-    uint32_t* meta) {
+    uint32_t* meta, uint32_t fixedLimit = 0) {
     if (len < 17 || len > (uint32_t)kMaxQuery) return;
     /* flags: QR/opcode/AA/TC clear, RD free; byte 3 must be zero */
     if (((q[2] & 0xFE) | q[3]) != 0) return;
@@ -337,7 +339,9 @@ __device__ __forceinline__ void resolveOneExtT(
         uint32_t m = nameWire;
         uint32_t e = ar != 0 ? (uint32_t)kOptLen : 0;
         if constexpr (kLim) {
-            if (t + e > (ar != 0 ? limit : (uint32_t)kSmallReply)) {
+            uint32_t lim = ar != 0 ? limit : (uint32_t)kSmallReply;
+            if (fixedLimit != 0) lim = fixedLimit;
+            if (t + e > lim) {
                 t = 12 + nameWire + 4;
                 m |= kMetaTrunc;
             }
@@ -473,6 +477,38 @@ __device__ inline uint32_t planTruncated(uint32_t meta, ExtJob* jobs) {
     if ((meta & kMetaEdns) == 0) return 1;
     jobs[1] = ExtJob{kSrcOpt, 0, (uint16_t)(12 + qlen), (uint16_t)kOptLen};
     return 2;
+}
+
+/* A group's first lane: cut each of the plan's first `heads` jobs that
+ * is above `chunk` bytes down to its first `chunk` and append the rest
+ * behind the plan's nj jobs as jobs of at most `chunk`. Returns the
+ * number of jobs. */
+__device__ inline uint32_t splitJobs(ExtJob* jobs, uint32_t nj,
+                                     uint32_t heads, uint32_t chunk) {
+    uint32_t end = nj;
+    for (uint32_t j = 0; j < heads; ++j) {
+        ExtJob jb = jobs[j];
+        if (jb.len <= chunk) continue;
+        jobs[j].len = (uint16_t)chunk;
+        for (uint32_t o = chunk; o < jb.len; o += chunk) {
+            uint32_t rest = jb.len - o;
+            jobs[end++] = ExtJob{jb.source, (uint16_t)(jb.src + o),
+                                 (uint16_t)(jb.dst + o),
+                                 (uint16_t)(rest < chunk ? rest : chunk)};
+        }
+    }
+    return end;
+}
+
+/* kGroup lanes make one copy of a plan into the reply at `dst` */
+static __device__ __forceinline__ void copyJob(ExtJob jb, uint8_t* dst,
+                                               const uint8_t* body,
+                                               const uint8_t* q,
+                                               uint32_t lane) {
+    const uint8_t* base = jb.source == kSrcBody    ? body
+                          : jb.source == kSrcQuery ? q
+                                                   : kOptSrc + 4;
+    groupCopy(dst + jb.dst, base + jb.src, jb.len, lane);
 }
 
 }  // namespace bamd::gpu

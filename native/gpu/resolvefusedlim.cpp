@@ -66,37 +66,6 @@ static_assert(kFusedPool >= kMaxExtJobs + kLargeReply / kFusedMinChunk);
 /* one bit per group in the listed word */
 static_assert(kFusedGroups <= 64);
 
-/* A group's first lane: cut each of the plan's first `heads` jobs that
- * is above `chunk` bytes down to its first `chunk` and append the rest
- * behind the plan's nj jobs as jobs of at most `chunk`. Returns the
- * number of jobs. */
-__device__ inline uint32_t splitJobs(ExtJob* jobs, uint32_t nj,
-                                     uint32_t heads, uint32_t chunk) {
-    uint32_t end = nj;
-    for (uint32_t j = 0; j < heads; ++j) {
-        ExtJob jb = jobs[j];
-        if (jb.len <= chunk) continue;
-        jobs[j].len = (uint16_t)chunk;
-        for (uint32_t o = chunk; o < jb.len; o += chunk) {
-            uint32_t rest = jb.len - o;
-            jobs[end++] = ExtJob{jb.source, (uint16_t)(jb.src + o),
-                                 (uint16_t)(jb.dst + o),
-                                 (uint16_t)(rest < chunk ? rest : chunk)};
-        }
-    }
-    return end;
-}
-
-static __device__ __forceinline__ void copyJob(ExtJob jb, uint8_t* dst,
-                                               const uint8_t* body,
-                                               const uint8_t* q,
-                                               uint32_t lane) {
-    const uint8_t* base = jb.source == kSrcBody    ? body
-                          : jb.source == kSrcQuery ? q
-                                                   : kOptSrc + 4;
-    groupCopy(dst + jb.dst, base + jb.src, jb.len, lane);
-}
-
 extern "C" __global__ __launch_bounds__(kFusedBlock)
 void bamd_resolve_fused_lim(
     const uint8_t* __restrict__ qbuf, const int32_t* __restrict__ qoff,

@@ -15,6 +15,7 @@
 #include "../engine/store.hpp"
 #include "../gpu/answerdelta.hpp"
 #include "../gpu/answerimage.hpp"
+#include "../gpu/frameindex.hpp"
 #include "../server/fastparse.hpp"
 #include "../zk/hostlist.hpp"
 
@@ -369,6 +370,24 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(py::bytes(q.name, q.nlen), q.isSrv,
                               (int)q.keyOff);
     });
+
+    /* where the bsock1 frames of a byte run start (gpu/frameindex.hpp),
+     * for the GPU resolver's frame bursts: (int32 [N + 1] frame starts
+     * as bytes, bytes consumed, status) */
+    m.attr("FRAME_INDEX_FULL") = (int)gpu::IndexStatus::Full;
+    m.attr("FRAME_INDEX_NEED_MORE") = (int)gpu::IndexStatus::NeedMore;
+    m.attr("FRAME_INDEX_BAD") = (int)gpu::IndexStatus::Bad;
+    m.def("frame_index",
+          [](py::bytes data, size_t maxFrames) {
+              std::string_view sv = std::string_view(data);
+              gpu::FrameIndex ix = gpu::frameIndex(
+                  (const uint8_t*)sv.data(), sv.size(), maxFrames);
+              return py::make_tuple(
+                  py::bytes((const char*)ix.foff.data(),
+                            ix.foff.size() * sizeof(int32_t)),
+                  ix.consumed, (int)ix.status);
+          },
+          py::arg("data"), py::arg("max_frames"));
 
     /* host image of an answer table for the GPU batch resolver
      * (gpu/answerimage.hpp); slots() and arena() hand out a verified
