@@ -100,11 +100,13 @@ $(PYMOD): $(CORE_OBJS) $(BUILD)/native/pybind/module.o
 
 # kernels, launcher and binding in one hipcc run; links amdhip64 only
 GPU_SRCS := native/gpu/resolve.cpp native/gpu/resolveext.cpp \
-	native/gpu/resolvelarge.cpp native/gpu/resolvefused.cpp \
+	native/gpu/resolvelarge.cpp native/gpu/resolvepolicy.cpp \
+	native/gpu/resolvefused.cpp \
 	native/gpu/resolvefusedlim.cpp native/gpu/resolveframes.cpp \
 	native/gpu/update.cpp native/gpu/pymodule.cpp
 $(GPUMOD): $(GPU_SRCS) native/gpu/resolve.hpp native/gpu/resolveext.hpp \
-		native/gpu/resolvelarge.hpp native/gpu/resolvefused.hpp \
+		native/gpu/resolvelarge.hpp native/gpu/resolvepolicy.hpp \
+		native/gpu/resolvefused.hpp \
 		native/gpu/resolvefusedlim.hpp native/gpu/resolveframes.hpp \
 		native/gpu/update.hpp \
 		native/gpu/devcopy.hpp \

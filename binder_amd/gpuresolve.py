@@ -22,7 +22,14 @@ ceiling, `_native.AnswerImage(max_reply=4096)`: replies of up to 4096
 bytes, each held against what its query may take (512 bytes, or the OPT
 record's size clamped to [512, 4096]) and truncated as the server
 truncates when it does not fit: header with TC, the question, the OPT
-tail. The table follows the registry through apply(): four more
+tail. With `policy=ZonePolicy(b"foo.com")` on top of that it runs a
+fourth pair (native/gpu/resolvepolicy.cpp), `bamd_resolve_lookup_pol` and
+`bamd_resolve_emit_pol`, which also writes the replies the server builds
+from the query alone: NOTIMP for a type it does not implement (AAAA, half
+of a dual-stack stub's capture), REFUSED for an SRV name of the wrong
+shape and for a name outside the zone. Those take no probe and no arena
+read; `tally=` counts what became of the batch in five device words. The
+table follows the registry through apply(): four more
 kernels (native/gpu/update.cpp) tombstone
 what a delta invalidates, claim or replace slots for what it upserts,
 and compact the table when dead space has built up. A query the image does not
@@ -96,10 +103,40 @@ FUSED_TILE = _gpuresolve.FUSED_TILE  # queries per fused workgroup
 OP_BLOCK = _gpuresolve.OP_BLOCK  # ops per update workgroup
 ACCEPT_EDNS = _gpuresolve.ACCEPT_EDNS        # ARCOUNT 1 with an OPT record
 ACCEPT_ANYCASE = _gpuresolve.ACCEPT_ANYCASE  # 'A'-'Z' in the name
+TALLY_WORDS = _gpuresolve.TALLY_WORDS  # counters of resolve(tally=...)
 
 
 def _pow2(n):
     return 1 << max(0, int(n) - 1).bit_length()
+
+
+class ZonePolicy:
+    """What resolve(..., policy=...) answers from the query alone, as the
+    server does: NOTIMP for a type other than A, SRV and PTR, REFUSED
+    for an SRV name that is not _svc._proto.domain, and with a zone
+    (the server's dnsDomain, bytes, e.g. b"foo.com") REFUSED for an A or
+    SRV name that is not a label or more under it. b"" is no zone rule.
+
+    The zone is lowercase [a-z0-9_-] labels of 1 to 63 bytes, at most
+    255 bytes in wire form, which is what the device keeps."""
+
+    _LABEL = frozenset(b"abcdefghijklmnopqrstuvwxyz0123456789_-")
+
+    def __init__(self, zone=b"", device="cuda"):
+        zone = bytes(zone)
+        wire = b""
+        if zone:
+            for label in zone.split(b"."):
+                if not 1 <= len(label) <= 63 or not self._LABEL.issuperset(
+                        label):
+                    raise ValueError(f"bad label in zone {zone!r}")
+                wire += bytes([len(label)]) + label
+            wire += b"\0"
+            if len(wire) > _gpuresolve.MAX_ZONE:
+                raise ValueError("zone above 255 bytes in wire form")
+        self.zone, self.wire = zone, wire
+        self._dev = torch.frombuffer(bytearray(wire or b"\0"),
+                                     dtype=torch.uint8).to(device)
 
 
 class GpuAnswerTable:
@@ -262,7 +299,8 @@ class GpuAnswerTable:
                 "arena_bytes": self._used, "dead_bytes": dead,
                 "compactions": self.compactions}
 
-    def resolve(self, qbuf, qoff, seed=0, accept=0, oversize=False):
+    def resolve(self, qbuf, qoff, seed=0, accept=0, oversize=False,
+                policy=None, tally=None):
         """qbuf: uint8 query bytes end to end; qoff: int32 [N + 1].
         Returns (rbuf uint8, roff int64 [N + 1]) on the device.
 
@@ -277,10 +315,31 @@ class GpuAnswerTable:
         size are left unserved. With oversize=True every accepted hit is
         served: in full when reply and OPT tail fit 512 bytes, or the
         advertised size clamped to [512, 4096], else truncated to the
-        header with TC set, the question as asked and the OPT tail."""
+        header with TC set, the question as asked and the OPT tail.
+
+        policy is a ZonePolicy and needs oversize=True. Every accepted
+        query that the server answers from the query alone then gets
+        that answer, whatever the table holds: NOTIMP or REFUSED, the
+        question as asked, and the OPT tail. Everything else is served
+        as without it; PTR stays unserved. tally, with policy only, is
+        an int64 device tensor of TALLY_WORDS counters that the call
+        adds to and never clears: served in full, truncated, NOTIMP,
+        REFUSED, unserved."""
         dev = self.device
         if accept & ~(ACCEPT_EDNS | ACCEPT_ANYCASE):
             raise ValueError(f"unknown accept bits: {accept:#x}")
+        if policy is not None and not isinstance(policy, ZonePolicy):
+            raise TypeError("policy must be a ZonePolicy")
+        if policy is not None and not oversize:
+            raise ValueError("policy needs oversize=True")
+        if tally is not None:
+            if policy is None:
+                raise ValueError("tally needs policy")
+            if tally.dtype != torch.int64 or tally.dim() != 1 or \
+                    tally.numel() != TALLY_WORDS or \
+                    not tally.is_contiguous() or tally.device.type != dev.type:
+                raise TypeError("tally must be a contiguous int64 tensor of "
+                                f"{TALLY_WORDS} words on the table's device")
         if qbuf.dtype != torch.uint8 or qoff.dtype != torch.int32:
             raise TypeError("qbuf must be uint8 and qoff int32")
         if qoff.dim() != 1 or qoff.numel() < 1 or qbuf.dim() != 1:
@@ -298,7 +357,16 @@ class GpuAnswerTable:
             batch = (qbuf.data_ptr(), qoff.data_ptr(), qbuf.numel(), n)
             body_off = torch.empty(n, dtype=torch.int32, device=dev)
             rlen = torch.empty(n, dtype=torch.int32, device=dev)
-            if oversize:
+            if policy is not None:
+                meta = torch.empty(n, dtype=torch.int32, device=dev)
+                zone = policy._dev.to(dev)  # held until the launch is queued
+                _gpuresolve.lookup_pol(
+                    *batch, self._slots.data_ptr(), self.cap,
+                    self._arena.data_ptr(), accept, zone.data_ptr(),
+                    len(policy.wire), body_off.data_ptr(), rlen.data_ptr(),
+                    meta.data_ptr(),
+                    0 if tally is None else tally.data_ptr(), stream)
+            elif oversize:
                 meta = torch.empty(n, dtype=torch.int32, device=dev)
                 _gpuresolve.lookup_lim(
                     *batch, self._slots.data_ptr(), self.cap,
@@ -318,7 +386,12 @@ class GpuAnswerTable:
             roff = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             roff[1:] = torch.cumsum(rlen, 0, dtype=torch.int64)
             rbuf = torch.empty(int(roff[-1]), dtype=torch.uint8, device=dev)
-            if rbuf.numel() != 0 and oversize:
+            if rbuf.numel() != 0 and policy is not None:
+                _gpuresolve.emit_pol(
+                    *batch, self._arena.data_ptr(), body_off.data_ptr(),
+                    rlen.data_ptr(), meta.data_ptr(), roff.data_ptr(),
+                    rbuf.data_ptr(), seed & (2 ** 64 - 1), stream)
+            elif rbuf.numel() != 0 and oversize:
                 _gpuresolve.emit_lim(
                     *batch, self._arena.data_ptr(), body_off.data_ptr(),
                     rlen.data_ptr(), meta.data_ptr(), roff.data_ptr(),
@@ -351,7 +424,8 @@ class GpuAnswerTable:
         it lies in the ring, and REPLY frames come out."""
         return FrameBurst(self, max_frames, max_bytes, rbuf)
 
-    def resolve_list(self, queries, seed=0, accept=0, oversize=False):
+    def resolve_list(self, queries, seed=0, accept=0, oversize=False,
+                     policy=None, tally=None):
         """One reply (bytes) or None per query."""
         offs = [0]
         for q in queries:
@@ -359,7 +433,8 @@ class GpuAnswerTable:
         qbuf = torch.frombuffer(bytearray(b"".join(queries) or b"\0"),
                                 dtype=torch.uint8)[:offs[-1]]
         qoff = torch.tensor(offs, dtype=torch.int32)
-        rbuf, roff = self.resolve(qbuf, qoff, seed, accept, oversize)
+        rbuf, roff = self.resolve(qbuf, qoff, seed, accept, oversize, policy,
+                                  tally)
         data, roff = rbuf.cpu().numpy().tobytes(), roff.tolist()
         return [data[a:b] if b > a else None
                 for a, b in zip(roff, roff[1:])]

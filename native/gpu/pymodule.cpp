@@ -15,6 +15,7 @@
 #include "resolvefused.hpp"
 #include "resolvefusedlim.hpp"
 #include "resolvelarge.hpp"
+#include "resolvepolicy.hpp"
 #include "update.hpp"
 
 namespace py = pybind11;
@@ -191,6 +192,59 @@ PYBIND11_MODULE(_gpuresolve, m) {
           py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
           py::arg("seed"), py::arg("stream"),
           py::arg("list_above") = kListAbove);
+
+    m.attr("MAX_ZONE") = kMaxZone;
+    m.attr("TALLY_WORDS") = (int)kTallyWords;
+
+    /* zone: zlen bytes of wire form (0: no zone rule); tally: 0, or
+     * TALLY_WORDS int64 counters that are added to */
+    m.def("lookup_pol",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t slots, uint64_t cap, uintptr_t arena,
+             uint32_t accept, uintptr_t zone, uint32_t zlen,
+             uintptr_t bodyOff, uintptr_t rlen, uintptr_t meta,
+             uintptr_t tally, uintptr_t stream) {
+              if (cap > 0x80000000u || (cap & (cap - 1)) != 0)
+                  throw std::invalid_argument("cap not a power of two");
+              if ((accept & ~kAcceptAll) != 0)
+                  throw std::invalid_argument("unknown accept bits");
+              if (zlen > kMaxZone || (zlen != 0 && zone == 0))
+                  throw std::invalid_argument("zone above MAX_ZONE bytes");
+              Image img{ptr<const void>(slots), (uint32_t)cap,
+                        ptr<const uint8_t>(arena)};
+              check(launchLookupPol(batch(qbuf, qoff, qbytes, n), img,
+                                    accept, ptr<const uint8_t>(zone), zlen,
+                                    ptr<uint32_t>(bodyOff),
+                                    ptr<int32_t>(rlen), ptr<uint32_t>(meta),
+                                    ptr<unsigned long long>(tally),
+                                    ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_lookup_pol");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("slots"), py::arg("cap"), py::arg("arena"),
+          py::arg("accept"), py::arg("zone"), py::arg("zlen"),
+          py::arg("body_off"), py::arg("rlen"), py::arg("meta"),
+          py::arg("tally"), py::arg("stream"));
+
+    m.def("emit_pol",
+          [](uintptr_t qbuf, uintptr_t qoff, int64_t qbytes, int64_t n,
+             uintptr_t arena, uintptr_t bodyOff, uintptr_t rlen,
+             uintptr_t meta, uintptr_t roff, uintptr_t rbuf, uint64_t seed,
+             uintptr_t stream) {
+              Image img{nullptr, 0, ptr<const uint8_t>(arena)};
+              check(launchEmitPol(batch(qbuf, qoff, qbytes, n), img,
+                                  ptr<const uint32_t>(bodyOff),
+                                  ptr<const int32_t>(rlen),
+                                  ptr<const uint32_t>(meta),
+                                  ptr<const int64_t>(roff),
+                                  ptr<uint8_t>(rbuf), seed,
+                                  ptr<ihipStream_t>(stream)),
+                    "bamd_resolve_emit_pol");
+          },
+          py::arg("qbuf"), py::arg("qoff"), py::arg("qbytes"), py::arg("n"),
+          py::arg("arena"), py::arg("body_off"), py::arg("rlen"),
+          py::arg("meta"), py::arg("roff"), py::arg("rbuf"),
+          py::arg("seed"), py::arg("stream"));
 
     m.attr("FUSED_TILE") = kFusedTile;
 

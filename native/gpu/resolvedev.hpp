@@ -1,9 +1,9 @@
 /*
- * binder-amd: device helpers shared by the three resolve kernel pairs
- * (resolve.cpp, resolveext.cpp, resolvelarge.cpp) and the fused kernels
- * (resolvefused.cpp, resolvefusedlim.cpp, resolveframes.cpp): the
- * streamed key and its hash, the member-order generator, the per-query
- * lookups and the copy plans of a reply.
+ * binder-amd: device helpers shared by the four resolve kernel pairs
+ * (resolve.cpp, resolveext.cpp, resolvelarge.cpp, resolvepolicy.cpp)
+ * and the fused kernels (resolvefused.cpp, resolvefusedlim.cpp,
+ * resolveframes.cpp): the streamed key and its hash, the member-order
+ * generator, the per-query lookups and the copy plans of a reply.
  * Device code only.
  */
 #pragma once
